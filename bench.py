@@ -1,6 +1,6 @@
-"""Headline benchmark: KL-NMF update-steps/sec (and wall-clock to fixed KL) at 96 x N, k = 50 (BASELINE.json).
+"""Headline benchmark: KL-NMF update-steps/sec (with ``--full`` also wall-clock to fixed KL) at 96 x N, k = 50 (BASELINE.json).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -11,23 +11,29 @@ Workload
   * ``--gpus 1``: config c2 of BASELINE.json, 96 x 100 000, k = 50 -- the configuration the metric is quoted on.
   * ``--gpus N`` (N > 1): config c3, 96 x 1 000 000 **in total**, the sample axis split over the ranks with
     ``distributed.shard_bounds`` (**strong scaling**); every step contains one RCCL all-reduce of the 50 x 96
-    numerator.  ``value`` = global update-steps/s of the whole job (NOT multiplied by N).  Rank 0 also runs the
-    same 10^6-sample problem alone on its GPU and reports that figure (``config.one_gpu_same_problem``) --
+    numerator.  ``value`` = global update-steps/s of the whole job (NOT multiplied by N).  With ``--full`` rank 0 also
+    runs the same 10^6-sample problem alone on its GPU and reports that figure (``config.one_gpu_same_problem``) --
     the number an N-GPU value has to be compared with; c2 at N = 1 is a different (10x smaller) problem.
     ``--weak`` restores round 1's weak-scaling reading (100 000 samples per GPU, value = N x global steps/s).
 
-Timing: W untimed warm-up steps, then blocks of EXACTLY K steps, each bracketed by barrier +
-stream/torch synchronisation on both sides; a rank's clock runs from the opening barrier to the completion of its own
-K steps, and the block's time is the maximum over the ranks (the closing barrier's own latency is not counted).  One block of 20 steps is 1.6 ms,
-too short to carry a number, so the block is repeated until the GPU has been busy for ~2.5 s and the line
-reports the MEDIAN block (``ms_per_step`` = median / K, with min / max / first block beside it).  Events and
-buffers are created by an untimed pass first.  Inputs are resident in HBM before any timed region.
+Timing: W untimed warm-up steps, then ONE block of EXACTLY K steps, bracketed by barrier + stream/torch synchronisation
+on both sides; a rank's clock runs from the opening barrier to the completion of its own K steps, and the block's time is
+the maximum over the ranks (the closing barrier's own latency is not counted).  ``value`` = K / that time and
+``ms_per_step`` = that time / K.  Inputs are resident in HBM before the timed region.  (N > 1 with a peer-to-peer
+exchange that passed its validation against RCCL: one such block through each, and the line reports the faster.)
 
-Rank 0 prints ONE JSON line.  ``roofline`` prices the dominant kernel (the fused update pass) on algorithmic
-flops 6*V*K*N_local against the fp64 MFMA peak; its duration is the mean over >= 100 launches sampled with HIP
-events on the engine's stream in a separate, untimed pass.  ``cpu_baseline`` times the NumPy oracle (the
-restated reference arithmetic) on this box's host cores (rank 0, N = 1 only); the same CPU run defines the
-target of ``time_to_kl``.  ``extra`` carries the other single-GPU configurations (c4 MvNMF, default-init fit).
+A plain run does only that: set up, warm up, time the K steps, write the outputs (``--dump-outputs DIR``: W and H as the
+timed steps left them, ``DIR/<name>.npy`` in float64, at most 64 MB in all; the inputs are seeded, so two builds run with
+the same arguments can be compared array for array) and print ONE JSON line on rank 0.
+
+``--full`` adds everything else, after the timed steps: the K-step block repeated until the GPU has been busy for ~2.5 s
+(median / min / max / first block under ``timing.repeated_blocks``); ``roofline``, which prices the dominant kernel (the
+fused update pass) on algorithmic flops 6*V*K*N_local against the fp64 MFMA peak, its duration the mean over >= 100
+launches sampled with HIP events on the engine's stream in a separate, untimed pass; ``cpu_baseline``, the NumPy oracle
+(the restated reference arithmetic) timed on this box's host cores, whose run also defines the target of ``time_to_kl``
+and the parity gate; ``extra``, the other single-GPU configurations (c4 MvNMF, default-init fit, fp32 fast mode, weighted
+step, c5, wide catalogues); and for N > 1 the per-rank exchange timeline, the ranks as the exchange layers report them and
+rank 0's one-GPU run of the same problem.
 """
 
 from __future__ import annotations
@@ -364,6 +370,35 @@ def extra_wide_catalogue(sal, device):
             "engines": res}
 
 
+DUMP_BYTES = 64 * 10**6  # --dump-outputs: at most this much in all (npy headers included)
+
+
+def dump_outputs(out_dir, W, H):
+    """What the timed path hands its caller -- the signatures ``W`` (K x V) and the exposures ``H`` (samples x K) after
+    the timed steps -- as ``out_dir/W.npy`` and ``out_dir/H.npy`` (float64).  Where H does not fit into DUMP_BYTES next to W,
+    a fixed sample of its rows (seed 0, in ascending order) is written instead, as ``H_rows_sample.npy`` with the row
+    numbers in ``H_rows_sample_index.npy``.  A directory this creates inside the repository carries a ``.gitignore`` of
+    its own, so that a dump leaves the work tree clean."""
+    out_dir = os.path.abspath(out_dir)
+    created = not os.path.isdir(out_dir)
+    os.makedirs(out_dir, exist_ok=True)
+    if created and out_dir.startswith(ROOT + os.sep):
+        with open(os.path.join(out_dir, ".gitignore"), "w") as fh:
+            fh.write("*\n")
+    arrays = {"W": W}
+    room = DUMP_BYTES - 3 * 4096 - W.nbytes  # (room for three npy headers)
+    if H.shape[0] * H.shape[1] * 8 <= room:
+        arrays["H"] = H
+    else:
+        rows = room // ((H.shape[1] + 1) * 8)  # (the sampled rows and their numbers)
+        idx = np.sort(np.random.default_rng(0).choice(H.shape[0], rows, replace=False))
+        arrays["H_rows_sample"] = H[idx]
+        arrays["H_rows_sample_index"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return sorted(arrays)
+
+
 def problem_rows(start, stop):
     """Rows [start, stop) of the 10^6-sample problem: 125 000-row blocks, block b drawn with seed b
     (per-shard seeds, no 8 GB host temporary).  W0 is block 0's."""
@@ -420,15 +455,20 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU oracle run (and time_to_kl)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra single-GPU configurations")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything else this file measures: repeated blocks, roofline, extra configurations, "
+                    "CPU baseline, time to KL and parity gate, and for N > 1 the exchange timeline and the one-GPU reference")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write W and H as the timed steps left them (rank 0: its rows of H) to DIR/<name>.npy, float64, <= 64 MB in all")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle run (and time_to_kl)")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the extra single-GPU configurations")
     ap.add_argument("--cpu-steps", type=int, default=500, help="CPU oracle steps that define the time-to-KL target")
     ap.add_argument("--cpu-budget", type=float, default=150.0, help="seconds after which the CPU run stops early")
     ap.add_argument("--cpu-steps-sharded", type=int, default=20, help="N > 1: CPU oracle steps on the whole sharded problem (each takes seconds)")
     ap.add_argument("--samples-total", type=int, default=0, help="override the total number of samples")
     ap.add_argument("--weak", action="store_true", help="N > 1: 100 000 samples per GPU instead of 10^6 in total")
-    ap.add_argument("--no-one-gpu-reference", action="store_true", help="N > 1: skip rank 0's run of the whole problem on one GPU")
-    ap.add_argument("--busy-seconds", type=float, default=2.5, help="repeat the K-step block until the GPU was busy this long")
+    ap.add_argument("--no-one-gpu-reference", action="store_true", help="N > 1, --full: skip rank 0's run of the whole problem on one GPU")
+    ap.add_argument("--busy-seconds", type=float, default=2.5, help="--full: repeat the K-step block until the GPU was busy this long")
     ap.add_argument("--no-p2p", action="store_true", help="N > 1: RCCL all-reduce only, do not try the peer-to-peer exchange")
     ap.add_argument("--simulate-no-rccl", action="store_true", help="rehearsal aid: behave as if the engine's RCCL communicator could not be created")
     ap.add_argument("--rehearse-one-device", action="store_true",
@@ -561,9 +601,8 @@ def main():
         dist.all_gather_object(out, obj)
         return out
 
-    # untimed: warm-up steps, and one profiling pass so that every event / lazily sized buffer exists
+    # untimed: the warm-up steps
     engine.kl_step(args.warmup)
-    engine.profile_kl_steps(8, 0, 2)
 
     def local_sync():
         engine.sync()
@@ -590,22 +629,23 @@ def main():
         barrier()
         return max_over_ranks(dt)
 
-    def timed_blocks():
+    def repeated_blocks():
+        """--full: the K-step block repeated until the GPU has been busy ``--busy-seconds``; (first, blocks, median)."""
         first = timed_block()
         if math.isinf(first):
-            return first, 0, [], first
+            return first, [], first
         n_blocks = int(min(1000, max(5, math.ceil(args.busy_seconds / max(first, 1e-6)))))
         blocks = []
         for _ in range(n_blocks):
             blocks.append(timed_block())
             if math.isinf(blocks[-1]):
-                return first, len(blocks), blocks, float("inf")
-        return first, n_blocks, blocks, statistics.median(blocks)
+                return first, blocks, float("inf")
+        return first, blocks, statistics.median(blocks)
 
     gpu_sections = {}  # wall-clock seconds of the sections in which the GPU is the one that works (launch gaps included)
     t_sec = time.perf_counter()
-    first, n_blocks, blocks, median = timed_blocks()
-    if math.isinf(median) and exchange is not None and exchange.get("p2p_valid") and rccl_ok:
+    block = timed_block()  # the measurement: value = K / block, ms_per_step = block / K
+    if math.isinf(block) and exchange is not None and exchange.get("p2p_valid") and rccl_ok:
         # the peer-to-peer exchange failed under load although it had passed its validation: every rank saw the infinite
         # block (MAX over ranks), so every rank comes here; the run goes on through RCCL and the line says so
         exchange["p2p_failed_during_timing"] = failures[-1] if failures else "on another rank"
@@ -614,35 +654,62 @@ def main():
         engine.upload_W(W0)
         engine.upload_H(H0)
         engine.kl_step(args.warmup)
-        first, n_blocks, blocks, median = timed_blocks()
-    if math.isinf(median):
+        block = timed_block()
+    if math.isinf(block):
         raise SystemExit(f"bench: the timed steps failed: {failures[-1] if failures else 'on another rank'}")
-    gpu_sections["timed_blocks"] = time.perf_counter() - t_sec
+    gpu_sections["timed_steps"] = time.perf_counter() - t_sec
     exchange_mode = "rccl" if sharded else None
     if exchange is not None and exchange.get("p2p_valid") and not rccl_ok:
-        exchange["p2p_ms_per_step"] = median / args.steps * 1e3
+        exchange["p2p_ms_per_step"] = block / args.steps * 1e3
         exchange_mode = "p2p"
     elif exchange is not None and exchange.get("p2p_valid"):
-        # the blocks above ran with the peer-to-peer exchange; the same protocol once more through RCCL
-        exchange["p2p_ms_per_step"] = median / args.steps * 1e3
+        # the block above ran with the peer-to-peer exchange; the same protocol once more through RCCL
+        exchange["p2p_ms_per_step"] = block / args.steps * 1e3
         engine.set_p2p(False)
         engine.kl_step(args.warmup)
-        r_first, r_n, r_blocks, r_median = timed_blocks()
-        exchange["rccl_ms_per_step"] = None if math.isinf(r_median) else r_median / args.steps * 1e3
-        if math.isinf(r_median):  # (RCCL itself failed: the peer-to-peer figure stands; the engine's state is restored)
+        r_block = timed_block()
+        exchange["rccl_ms_per_step"] = None if math.isinf(r_block) else r_block / args.steps * 1e3
+        if math.isinf(r_block):  # (RCCL itself failed: the peer-to-peer figure stands; the engine's state is restored)
             exchange["rccl_failed_during_timing"] = failures[-1] if failures else "on another rank"
             engine.set_p2p(True)
             engine.upload_W(W0)
             engine.upload_H(H0)
             engine.kl_step(args.warmup)
             exchange_mode = "p2p"
-        elif r_median < median:
-            first, n_blocks, blocks, median = r_first, r_n, r_blocks, r_median
+        elif r_block < block:
+            block = r_block
         else:
             engine.set_p2p(True)
             exchange_mode = "p2p"
     if exchange is not None:
         exchange["used_for_value"] = exchange_mode
+
+    # what the timed path computed: W and H as its last step left them (rank 0: W, replicated, and its rows of H)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, engine.download_W(), engine.download_H())
+
+    timing = {"timed_steps": args.steps, "block_ms": block * 1e3}
+    objective = fused_ms = tail_ms = fwd_ms = wh_ms = None
+    if args.full:
+        # the K-step block repeated as long as --busy-seconds asks (after the timed steps: their figure is the line's value)
+        t_sec = time.perf_counter()
+        r_first, r_blocks, r_median = repeated_blocks()
+        gpu_sections["repeated_blocks"] = time.perf_counter() - t_sec
+        if math.isinf(r_median):
+            timing["repeated_blocks"] = {"error": failures[-1] if failures else "on another rank"}
+        else:
+            timing["repeated_blocks"] = {
+                "blocks": len(r_blocks),
+                "steps_per_block": args.steps,
+                "block_ms_median": r_median * 1e3,
+                "block_ms_min": min(r_blocks) * 1e3,
+                "block_ms_max": max(r_blocks) * 1e3,
+                "first_block_ms": r_first * 1e3,
+                "ms_per_step_median": r_median / args.steps * 1e3,
+                "ms_per_step_best_block": min(r_blocks) / args.steps * 1e3,
+            }
+    if args.full and exchange is not None:
         # where a sharded step's microseconds go, rank by rank (untimed; same launches, HIP events on the two dispatches
         # and s_memrealtime stamps around the exchange inside the tail): printed with the line, so that the first run on a
         # node says whether compute, the exchange's wire time or the ranks' skew (wait_for_peer_flags) is the long pole
@@ -690,17 +757,18 @@ def main():
         exchange["p2p_nranks"] = min((r.get("p2p_nranks", 0) for r in rows), default=0)
         exchange["distinct_devices"] = len({r.get("pci_bus_id") for r in rows if r.get("pci_bus_id")})
 
-    # untimed: kernel durations from HIP events bound to the dispatches of every 2nd step of 200 (100 samples each)
-    barrier()
-    t_sec = time.perf_counter()
-    _, fused_ms, tail_ms = engine.profile_kl_steps(200, 0, 2)
-    objective = engine.objective()
-    fwd_ms = engine.profile_objective(20)
-    wh_ms = engine.profile_reconstruct(20)
-    gpu_sections["kernel_samples"] = time.perf_counter() - t_sec
-    barrier()
+    if args.full:
+        # untimed: kernel durations from HIP events bound to the dispatches of every 2nd step of 200 (100 samples each)
+        barrier()
+        t_sec = time.perf_counter()
+        _, fused_ms, tail_ms = engine.profile_kl_steps(200, 0, 2)
+        objective = engine.objective()
+        fwd_ms = engine.profile_objective(20)
+        wh_ms = engine.profile_reconstruct(20)
+        gpu_sections["kernel_samples"] = time.perf_counter() - t_sec
+        barrier()
 
-    # From here on nothing may cost the headline line (the timed blocks above are the measurement): what only rank 0 does is
+    # From here on (--full) nothing may cost the headline line (the timed steps above are the measurement): what only rank 0 does is
     # wrapped on rank 0, and what all ranks do together is wrapped with the collectives OUTSIDE the guarded part, so that a
     # rank that failed still meets the others.
     one_gpu = None
@@ -711,7 +779,7 @@ def main():
             whole.extend(problem_rows(0, n_total))
         return whole[0], whole[1]
 
-    if strong and not args.no_one_gpu_reference:
+    if strong and args.full and not args.no_one_gpu_reference:
         # the same problem on ONE GPU (rank 0's), the figure the N-GPU value is to be compared with
         if rank == 0:
             try:
@@ -739,7 +807,8 @@ def main():
                     "n_samples": n_total,
                     "ms_per_step": t1 * 1e3,
                     "steps_per_s": 1.0 / t1,
-                    "speedup_of_this_run": (args.steps / median) * t1,
+                    # (against the repeated blocks' median: the same protocol on both sides)
+                    "speedup_of_this_run": (args.steps / (block if math.isinf(r_median) else r_median)) * t1,
                     "how": f"rank 0 alone, median of {len(ts)} blocks of {args.steps} steps after {max(args.warmup, 5)} warm-up steps (the timed blocks' protocol), "
                            f"same {n_total}-sample problem"
                     + (" (the other ranks' engines idle on the SAME device: rehearsal)" if args.rehearse_one_device else ""),
@@ -754,7 +823,7 @@ def main():
     # decision), and once more for exactly the CPU path's number of steps: the north star's parity gate on the sharded run
     # (W, replicated, on every rank; H on rank 0's rows).
     sharded_cpu, sharded_ttk = None, None
-    if strong and not args.no_cpu_baseline:
+    if strong and args.full and not args.no_cpu_baseline:
         box = [None]
         W_cpu = H_cpu = None
         if rank == 0:
@@ -819,21 +888,7 @@ def main():
         barrier()
 
     if rank == 0:
-        flops_step = 6.0 * V * K * n_local  # algorithmic flops of one launch of the fused kernel
-        achieved = flops_step / (fused_ms * 1e-3) / 1e12
-        traffic, traffic_source = None, None
-        pmc = os.path.join(ROOT, "profiles", "pmc_summary.json")
-        if os.path.exists(pmc):
-            try:
-                rec = json.load(open(pmc))
-                traffic = rec.get("fused_kernel_hbm_bytes_per_launch") if n_local == N_C2 else None  # measured at c2 only
-                traffic_source = (
-                    f"NOT measured in this run: profiles/pmc_summary.json ({rec.get('date', 'round 1')}), rocprofv3 --pmc "
-                    "FETCH_SIZE / WRITE_SIZE passes of this command at c2 (FETCH x2 gfx950 correction applied)"
-                )
-            except Exception:
-                traffic = None
-        steps_per_s = args.steps / median
+        steps_per_s = args.steps / block
         line = {
             "metric": "KL-NMF update-steps/sec (96xN, k=50)",
             "value": steps_per_s * (world if (sharded and not strong) else 1),
@@ -841,7 +896,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
-            "ms_per_step": median / args.steps * 1e3,
+            "ms_per_step": block / args.steps * 1e3,
             "higher_is_better": True,
             "scaling": ("strong" if strong else "weak") if sharded else "n/a",
             "vs_baseline": None,
@@ -866,19 +921,29 @@ def main():
                 ),
                 "exchange": exchange,
                 "global_steps_per_s": steps_per_s,
-                "objective_after_run": objective,
-                "one_gpu_same_problem": one_gpu,
             },
-            "timing": {
-                "blocks": n_blocks,
-                "steps_per_block": args.steps,
-                "block_ms_median": median * 1e3,
-                "block_ms_min": min(blocks) * 1e3,
-                "block_ms_max": max(blocks) * 1e3,
-                "first_block_ms": first * 1e3,
-                "ms_per_step_best_block": min(blocks) / args.steps * 1e3,
-            },
-            "roofline": {
+            "timing": timing,
+        }
+        if dumped is not None:
+            line["outputs"] = dumped
+        if args.full:
+            flops_step = 6.0 * V * K * n_local  # algorithmic flops of one launch of the fused kernel
+            achieved = flops_step / (fused_ms * 1e-3) / 1e12
+            traffic, traffic_source = None, None
+            pmc = os.path.join(ROOT, "profiles", "pmc_summary.json")
+            if os.path.exists(pmc):
+                try:
+                    rec = json.load(open(pmc))
+                    traffic = rec.get("fused_kernel_hbm_bytes_per_launch") if n_local == N_C2 else None  # measured at c2 only
+                    traffic_source = (
+                        f"NOT measured in this run: profiles/pmc_summary.json ({rec.get('date', 'round 1')}), rocprofv3 --pmc "
+                        "FETCH_SIZE / WRITE_SIZE passes of this command at c2 (FETCH x2 gfx950 correction applied)"
+                    )
+                except Exception:
+                    traffic = None
+            line["config"]["objective_after_run"] = objective
+            line["config"]["one_gpu_same_problem"] = one_gpu
+            line["roofline"] = {
                 "bound": "mfma",
                 "kernel": "fused_kernel<13,3,2,G,U> (P=H.W, R=X/P, G+=H^T.R, U=R.W^T, H update)",
                 "achieved": achieved,
@@ -891,13 +956,12 @@ def main():
                 "kernel_avg_ms": fused_ms,
                 "kernel_samples": 100,
                 "tail_avg_ms": tail_ms,
-                "step_frac_of_peak": flops_step / (median / args.steps) / 1e12 / FP64_MFMA_PEAK_TFLOPS,
+                "step_frac_of_peak": flops_step / (block / args.steps) / 1e12 / FP64_MFMA_PEAK_TFLOPS,
                 "forward_objective_kernel_ms": fwd_ms,
                 "forward_WH_frac": 2.0 * V * K * n_local / (fwd_ms * 1e-3) / 1e12 / FP64_MFMA_PEAK_TFLOPS,
                 "WH_only_kernel_ms": wh_ms,
                 "WH_only_frac": 2.0 * V * K * n_local / (wh_ms * 1e-3) / 1e12 / FP64_MFMA_PEAK_TFLOPS,
-            },
-        }
+            }
         engine.close()
         if sharded_cpu is not None:
             line["cpu_baseline"] = sharded_cpu
@@ -914,7 +978,7 @@ def main():
                 f"{world} ranks as processes on ONE GPU (device 0), control plane gloo, no RCCL, peer-to-peer exchange between the "
                 "processes: a rehearsal of the --gpus N flow, NOT a scaling measurement"
             )
-        if not sharded:
+        if not sharded and args.full:
             # the other single-GPU configurations FIRST, the CPU baseline (100 s of NumPy on the host cores, the GPU idle)
             # last: a utilisation trace of this process shows the device at work for the first part of the run, then nothing
             if not args.no_extra:
@@ -938,10 +1002,11 @@ def main():
                 line["parity"] = {k: line["time_to_kl"][k] for k in ("parity_steps", "rel_l2_W", "rel_l2_H", "parity_gate", "parity_ok")}
                 gpu_sections["time_to_kl"] = time.perf_counter() - t_sec
                 line["cpu_baseline_wall_seconds"] = cpu_wall
-        # where this process's wall clock went: the GPU works in the sections listed (the timed blocks are pure device
-        # time; the extras include host-side data generation), it idles during the CPU baseline
-        line["gpu_seconds_total"] = sum(gpu_sections.values())
-        line["gpu_sections_seconds"] = gpu_sections
+        if args.full:
+            # where this process's wall clock went: the GPU works in the sections listed (the timed blocks are pure device
+            # time; the extras include host-side data generation), it idles during the CPU baseline
+            line["gpu_seconds_total"] = sum(gpu_sections.values())
+            line["gpu_sections_seconds"] = gpu_sections
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(line) + "\n").encode())
     else:

@@ -10,7 +10,7 @@ export C5_ONLY_FULL=1
 WORKLOADS=${@:-bench mv c5}
 for w in $WORKLOADS; do
   case $w in
-    bench) CMD="python3 $REPO/bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-extra --busy-seconds 0.2" ;;
+    bench) CMD="python3 $REPO/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-extra --busy-seconds 0.2" ;;
     mv)    CMD="python3 $REPO/tools/bench_mv.py" ;;
     c5)    CMD="python3 $REPO/tools/bench_c5.py" ;;
   esac
