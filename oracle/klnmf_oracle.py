@@ -344,3 +344,80 @@ def synthetic_problem(V, N, K, seed=0, mean_mutations=2000.0):
     W0 = np.clip(W0 / s[:, None], EPSILON, None)
     H0 = np.clip(H0 * s[None, :], EPSILON, None)
     return X, W0, H0
+
+
+# --------------------------------------------------------------------------- sparse catalogues (the clip floor)
+
+
+def sparse_problem(V, N, K, seed=0, alpha=0.1, active=(1, 4), mutations=(20, 400), n_zero_samples=None, n_dead_channels=None):
+    """A sparse mutation catalogue whose fit drives a large share of W and H to the EPSILON floor.
+
+    Truth: ``K`` signatures drawn from ``Dirichlet(alpha)``; each sample uses ``active`` (inclusive range) of them, with
+    exact zeros elsewhere, and carries a number of mutations drawn uniformly from ``mutations``.  A few samples are all
+    zero and a few channels are never observed (their truth is 0 in every signature).  X is clipped at EPSILON as
+    ``_setup_adata`` does (``signature_nmf.py:281``).  The initialisation is that of :func:`synthetic_problem`.
+
+    Returns sample-major ``X (N, V)``, ``W0 (K, V)``, ``H0 (N, K)``.
+    """
+    rng = np.random.default_rng(seed)
+    n_zero = max(1, N // 200) if n_zero_samples is None else int(n_zero_samples)
+    n_dead = max(1, V // 48) if n_dead_channels is None else int(n_dead_channels)
+    W_true = rng.dirichlet(np.full(V, alpha), size=K)  # (K, V)
+    dead = rng.choice(V, size=min(n_dead, V - 1), replace=False)
+    W_true[:, dead] = 0.0
+    W_true /= np.maximum(W_true.sum(axis=1, keepdims=True), np.finfo(np.float64).tiny)
+    n_active = np.minimum(K, rng.integers(active[0], active[1] + 1, size=N))
+    on = np.argsort(rng.random((N, K)), axis=1).argsort(axis=1) < n_active[:, None]  # n_active[n] random columns per row
+    share = np.where(on, rng.gamma(1.0, 1.0, size=(N, K)), 0.0)  # Dirichlet(1) over the active columns
+    H_true = share / share.sum(axis=1, keepdims=True) * rng.integers(mutations[0], mutations[1] + 1, size=N)[:, None]
+    H_true[rng.choice(N, size=min(n_zero, N), replace=False)] = 0.0
+    X = rng.poisson(H_true @ W_true).astype(np.float64)
+    X = np.clip(X, EPSILON, None)
+    W0 = rng.dirichlet(np.ones(V), size=K)
+    H0 = X.sum(axis=1)[:, None] * rng.dirichlet(np.ones(K), size=N)
+    s = W0.sum(axis=1)
+    W0 = np.clip(W0 / s[:, None], EPSILON, None)
+    H0 = np.clip(H0 * s[None, :], EPSILON, None)
+    return X, W0, H0
+
+
+def floor_state(V, N, K, seed=0, steps=30, weights_kl=None, weights_lhalf=None, n_given=0, **kwargs):
+    """``steps`` joint updates of the oracle on :func:`sparse_problem`: a state with a large share of W and H at the floor.
+
+    Returns sample-major ``X (N, V)``, ``W (K, V)``, ``H (N, K)``."""
+    X, W, H = sparse_problem(V, N, K, seed, **kwargs)
+    Xt, Wt, Ht = X.T, W.T, H.T
+    for _ in range(steps):
+        Wt, Ht = update_WH(Xt, Wt, Ht, weights_kl, weights_lhalf, n_given)
+    return X, np.ascontiguousarray(Wt.T), np.ascontiguousarray(Ht.T)
+
+
+def update_WH_preclip(X, W, H, weights_kl=None, weights_lhalf=None, n_given_signatures=0):
+    """:func:`update_WH` before its final clips: ``(W_pre, H_pre, t, disc)`` in reference shapes.
+
+    ``W_pre`` has the given columns restored (as ``:338``) but nothing clipped; with all signatures given it is ``W``
+    itself.  ``H_pre`` is the multiplicative update, or with l-half weights ``0.25 t^2 (/ w_kl^2)`` with
+    ``t = w_lh/2 - sqrt(disc)``; ``t`` and ``disc`` are ``None`` without l-half weights."""
+    X, W, H = (np.asarray(a, dtype=np.float64) for a in (X, W, H))
+    K = W.shape[1]
+    g = int(n_given_signatures)
+    aux = _ratio(X, W, H)
+    if g == K:
+        Wp = W.copy()
+    else:
+        scaled = aux if weights_kl is None else weights_kl * aux
+        Wp = W * (scaled @ H.T)
+        Wp = Wp / Wp.sum(axis=0)
+        Wp[:, :g] = W[:, :g]
+    factor = W.T @ aux
+    if weights_lhalf is None:
+        return Wp, H * factor, None, None
+    inter = 4.0 * H * factor
+    if weights_kl is not None:
+        inter = inter * weights_kl**2
+    disc = 0.25 * weights_lhalf**2 + inter
+    t = weights_lhalf / 2 - np.sqrt(disc)
+    Hp = 0.25 * t**2
+    if weights_kl is not None:
+        Hp = Hp / weights_kl**2
+    return Wp, Hp, t, disc

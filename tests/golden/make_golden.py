@@ -20,6 +20,10 @@ Outputs (all float64):
   corr_synth.npz    correlated NMF (row f1): every function of _utils_corrnmf and a 3-update CorrNMFDet
                     trajectory on synthetic counts, K in {7, 12} -- run with ``--corr`` (only this file is
                     regenerated; the embedding solves go through the installed SciPy, as in the reference)
+  kl_floor.npz      a sparse 96-feature catalogue whose fit sits on the EPSILON clip floor (``--floor``; only this file
+                    is regenerated): update_WH with 0, 3 and all signatures given, update_W / update_H with and without
+                    l-half, both divergences, one MvNMF step, given rows holding 0 / 1e-12 / 1e-9, and a channel that is 0
+                    in every given signature (P == 0: the inf / NaN the reference returns there)
   corr_c5.npz       the embedding solves at the instantiations config c5 uses -- run with ``--corr-c5``
                     (~15 min: the reference's Hessian is a Python triple loop without numba): joint sample solves with
                     ns_signatures [40, 40], dim 40, V = 96 / 83 at the start and after two reference-executed updates of
@@ -297,6 +301,60 @@ def corr_c5_golden(uk, uc):
     print("corr_c5.npz written (scipy", scipy.__version__ + f", {time.time() - t0:.0f} s)")
 
 
+def floor_golden(uk, mv):
+    """kl_floor.npz: the reference's functions on a state where a large share of W and H sits at the EPSILON floor."""
+    sys.path.insert(0, REPO)
+    from oracle.klnmf_oracle import sparse_problem  # input generator only
+
+    EPS = uk.EPSILON
+    V, N, K, g = 96, 160, 8, 3
+    Xs, W0, H0 = sparse_problem(V, N, K, seed=71, active=(1, 2))
+    X, W, H = Xs.T.copy(), W0.T.copy(), H0.T.copy()  # reference shapes (V,N), (V,K), (K,N)
+    for _ in range(30):
+        W, H = uk.update_WH(X, W, H)
+    # given columns with entries below the floor: exact zeros, 1e-12 and 1e-9 (COSMIC-style signatures have them)
+    rng = np.random.default_rng(72)
+    for k in range(g):
+        rows = rng.choice(V, size=12, replace=False)
+        W[rows[:4], k], W[rows[4:8], k], W[rows[8:], k] = 0.0, 1e-12, 1e-9
+    wkl = rng.uniform(0.5, 2.0, N)
+    wlh = rng.uniform(0.0, 60.0, N)  # large enough to push exposures to the floor through the l-half root
+    out = dict(X=X, W=W, H=H, wkl=wkl, wlh=wlh, n_given=g)
+    for tag, ng in (("g0", 0), ("g3", g), ("gK", K)):
+        out[f"WH_{tag}_W"], out[f"WH_{tag}_H"] = uk.update_WH(X, W.copy(), H.copy(), None, None, ng)
+    out["WH_lh_W"], out["WH_lh_H"] = uk.update_WH(X, W.copy(), H.copy(), wkl, wlh, g)
+    out["W_g0"] = uk.update_W(X, W.copy(), H.copy())
+    out["W_g3"] = uk.update_W(X, W.copy(), H.copy(), None, g)
+    out["W_g3_wkl"] = uk.update_W(X, W.copy(), H.copy(), wkl, g)
+    out["H_plain"] = uk.update_H(X, W.copy(), H.copy())
+    out["H_lh"] = uk.update_H(X, W.copy(), H.copy(), wkl, wlh)
+    out["H_lh_nokl"] = uk.update_H(X, W.copy(), H.copy(), None, wlh)
+    out["kl"] = uk.kl_divergence(X, W, H)
+    out["kl_w"] = uk.kl_divergence(X, W, H, wkl)
+    out["skl"] = uk.samplewise_kl_divergence(X, W, H)
+    lam, delta = 1.0, 1.0
+    for tag, ng in (("g0", 0), ("g3", g)):
+        Hm = uk.update_H(X, W.copy(), H.copy())
+        Wu = mv.update_W_unconstrained(X, W.copy(), Hm, lam, delta, ng)
+        Wn, Hn, gamma = mv.line_search(X, W.copy(), Hm, lam, delta, 1.0, Wu)
+        out.update({f"mv_{tag}_H": Hm, f"mv_{tag}_Wunc": Wu, f"mv_{tag}_W": Wn, f"mv_{tag}_Hn": Hn, f"mv_{tag}_gamma": gamma})
+    out["mv_par"] = np.array([lam, delta])
+    # P == 0: every signature given, channel 0 is 0 in all of them -- X / (W H) meets 0 / 0 and x / 0 there
+    Wz = W.copy()
+    Wz[0] = 0.0
+    Xz = X.copy()
+    Xz[0, ::2] = 0.0  # half of the samples observe nothing in that channel, the others EPSILON or counts
+    Xz[0, 1::4] = 3.0
+    out.update(Xz=Xz, Wz=Wz)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["z_kl"] = uk.kl_divergence(Xz, Wz, H)
+        out["z_skl"] = uk.samplewise_kl_divergence(Xz, Wz, H)
+        out["z_WH_W"], out["z_WH_H"] = uk.update_WH(Xz, Wz.copy(), H.copy(), None, None, K)
+        out["z_H"] = uk.update_H(Xz, Wz.copy(), H.copy())
+    np.savez_compressed(os.path.join(HERE, "kl_floor.npz"), **out)
+    print("kl_floor.npz written: H at the floor %.2f, W %.2f" % ((H == EPS).mean(), (W == EPS).mean()))
+
+
 def main():
     if not os.path.isdir(REF):
         print("no /root/reference here: nothing to do")
@@ -304,6 +362,9 @@ def main():
     uk, mv = load_reference()
     if "--corr" in sys.argv:
         corr_golden(uk, load_reference_corrnmf())
+        return
+    if "--floor" in sys.argv:
+        floor_golden(uk, mv)
         return
     if "--corr-c5" in sys.argv:
         corr_c5_golden(uk, load_reference_corrnmf())
