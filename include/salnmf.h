@@ -408,6 +408,40 @@ int salnmf_profile_objective(salnmf_engine* e, int n_calls, double* avg_ms);
 /* Same for the forward kernel alone (H @ W written to a scratch buffer, no objective terms). */
 int salnmf_profile_reconstruct(salnmf_engine* e, int n_calls, double* avg_ms);
 
+/* ---- Batched sweeps (KLNMFSweep, salamander_amd/models/sweep.py): many independent KLNMF models -- different
+ * n_signatures, different initialisations -- on ONE count matrix, one workgroup per model, every model's step, objective
+ * and per-sample divergences in one launch for all of them.  What the reference's tutorial does one fit after another to
+ * choose the number of signatures (tutorial.ipynb section 1.6: KLNMF(n_signatures=k).fit(adata.copy()) for k = 1..9).
+ * Limits: n_features <= 96, n_samples <= 1024 (64 tiles of 16), 1 <= n_signatures <= 16 per member, unweighted.  Every
+ * member's W, H and objectives are bit for bit what an engine of that shape computes (salnmf_kl_step,
+ * salnmf_objective_async, salnmf_samplewise_kl): the step is the small-cohort kernel's body, the passes restate the forward
+ * kernel with the engine's grid (csrc/salnmf_batch.h).  Errors of these entry points: salnmf_batch_last_error. */
+typedef struct salnmf_batch salnmf_batch;
+#define SALNMF_BATCH_SLOTS 256 /* rows of the objective array: one row per convergence test, one column per member */
+const char* salnmf_batch_last_error(void);
+/* n_signatures: n_members values.  Members are numbered 0 .. n_members - 1 in that order. */
+int salnmf_batch_create(int device, int n_features, int64_t n_samples, int n_members, const int* n_signatures,
+                        salnmf_batch** out);
+void salnmf_batch_destroy(salnmf_batch* b);
+/* The count matrix (n_samples x n_features) shared by all members; clip != 0: X.clip(EPSILON) on the way, as
+ * SignatureNMF._setup_adata does (signature_nmf.py:281). */
+int salnmf_batch_upload_X(salnmf_batch* b, const double* X, int clip);
+/* One member's initial W (n_signatures x n_features) and H (n_samples x n_signatures), as salnmf_upload_W / _H. */
+int salnmf_batch_upload_member(salnmf_batch* b, int member, const double* W, const double* H);
+int salnmf_batch_download_member(salnmf_batch* b, int member, double* W, double* H);
+/* n_steps joint updates (update_WH, _utils_klnmf.py:281-361) of each listed member, n_given[i] of member members[i]'s
+ * first signatures kept (0 <= n_given[i] < its n_signatures); one launch of n_active workgroups per 4 096 steps.  Members
+ * not listed are left as they are. */
+int salnmf_batch_kl_step(salnmf_batch* b, int n_steps, int n_active, const int* members, const int* n_given);
+/* KLNMF.objective_function (klnmf.py:64-80, kl_divergence _utils_klnmf.py:11-55) of each listed member into row `slot` of
+ * the objective array (pinned host memory, written by the reducing workgroup), no host round trip.  Entries of members not
+ * listed keep what they held. */
+int salnmf_batch_objective_async(salnmf_batch* b, int slot, int n_active, const int* members);
+/* Rows [first, first + count) of the objective array -> out (count x n_members): waits for those rows only. */
+int salnmf_batch_objective_read(salnmf_batch* b, int first, int count, double* out);
+/* samplewise_kl_divergence (_utils_klnmf.py:58-97) of every member -> out (n_members x n_samples). */
+int salnmf_batch_samplewise_kl(salnmf_batch* b, double* out);
+
 #ifdef __cplusplus
 }
 #endif

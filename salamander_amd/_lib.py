@@ -104,9 +104,21 @@ SIGNATURES = {
     "salnmf_profile_objective": (c_int, [_P, c_int, _D]),
     "salnmf_profile_sharded_steps": (c_int, [_P, c_int, c_int, POINTER(c_double)]),
     "salnmf_profile_reconstruct": (c_int, [_P, c_int, _D]),
+    # batched sweeps (KLNMFSweep): salamander_amd/batch.py
+    "salnmf_batch_last_error": (c_char_p, []),
+    "salnmf_batch_create": (c_int, [c_int, c_int, c_int64, c_int, POINTER(c_int), POINTER(_P)]),
+    "salnmf_batch_destroy": (None, [_P]),
+    "salnmf_batch_upload_X": (c_int, [_P, _D, c_int]),
+    "salnmf_batch_upload_member": (c_int, [_P, c_int, _D, _D]),
+    "salnmf_batch_download_member": (c_int, [_P, c_int, _D, _D]),
+    "salnmf_batch_kl_step": (c_int, [_P, c_int, c_int, POINTER(c_int), POINTER(c_int)]),
+    "salnmf_batch_objective_async": (c_int, [_P, c_int, c_int, POINTER(c_int)]),
+    "salnmf_batch_objective_read": (c_int, [_P, c_int, c_int, _D]),
+    "salnmf_batch_samplewise_kl": (c_int, [_P, _D]),
 }
 
 OBJECTIVE_SLOTS = 256  # SALNMF_OBJECTIVE_SLOTS
+BATCH_SLOTS = 256  # SALNMF_BATCH_SLOTS
 BUILD_PERSISTENT = 1  # salnmf_build_flags(): the library carries the persistent multi-step kernel
 
 _lib = None
@@ -198,3 +210,10 @@ def last_error() -> str:
 def check(rc: int) -> None:
     if rc != 0:
         raise RuntimeError(f"salnmf: {last_error()}")
+
+
+def check_batch(rc: int) -> None:
+    """``check`` for the ``salnmf_batch_*`` entry points, which report through ``salnmf_batch_last_error``."""
+    if rc != 0:
+        msg = load().salnmf_batch_last_error()
+        raise RuntimeError(f"salnmf: {msg.decode() if msg else ''}")

@@ -1,0 +1,107 @@
+"""Python handle of one device batch: many KLNMF models of at most 16 signatures on one count matrix (``KLNMFSweep``).
+
+Thin, in the style of ``engine.py``: validates shapes, hands plain pointers to the ``salnmf_batch_*`` entry points of
+``include/salnmf.h`` and turns status codes into exceptions.  Members are numbered in the order of ``n_signatures``;
+arrays are in AnnData's storage layout (``X (N, V)``, ``W (K, V)``, ``H (N, K)``, float64, C order).
+"""
+
+from __future__ import annotations
+
+import ctypes
+from ctypes import POINTER, c_double, c_int
+
+import numpy as np
+
+from . import _lib
+from .engine import _as_c, _ptr
+
+SLOTS = _lib.BATCH_SLOTS
+MAX_SAMPLES = 1024  # 64 tiles of 16 samples (the small-cohort kernel's reach)
+MAX_FEATURES = 96
+MAX_SIGNATURES = 16
+
+
+def _ints(values) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(values, dtype=np.int32).reshape(-1))
+
+
+def _iptr(a):
+    return a.ctypes.data_as(POINTER(c_int))
+
+
+class BatchEngine:
+    """Device-resident state of a sweep: X once, W / H / numerator per member."""
+
+    def __init__(self, n_samples: int, n_features: int, n_signatures, device: int = 0):
+        self._lib = _lib.load()
+        if self._lib.salnmf_device_count() < 1:
+            raise _lib.EngineUnavailable(
+                "no HIP device visible: salamander_amd runs on MI355X (gfx950) only and has no CPU fallback."
+            )
+        self.N, self.V, self.device = int(n_samples), int(n_features), int(device)
+        self.Ks = [int(k) for k in n_signatures]
+        self.M = len(self.Ks)
+        ks = _ints(self.Ks)
+        handle = ctypes.c_void_p()
+        _lib.check_batch(self._lib.salnmf_batch_create(self.device, self.V, self.N, self.M, _iptr(ks), ctypes.byref(handle)))
+        self._handle = handle
+
+    @property
+    def _h(self):
+        h = getattr(self, "_handle", None)
+        if not h:
+            raise RuntimeError("salnmf: this BatchEngine has been closed")
+        return h
+
+    def close(self):
+        if getattr(self, "_handle", None):
+            self._lib.salnmf_batch_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def upload_X(self, X, clip: bool = False):
+        X = _as_c(X, (self.N, self.V), "X")
+        _lib.check_batch(self._lib.salnmf_batch_upload_X(self._h, _ptr(X), int(bool(clip))))
+
+    def upload_member(self, member: int, W, H):
+        K = self.Ks[member]
+        W = _as_c(W, (K, self.V), "W")
+        H = _as_c(H, (self.N, K), "H")
+        _lib.check_batch(self._lib.salnmf_batch_upload_member(self._h, int(member), _ptr(W), _ptr(H)))
+
+    def download_member(self, member: int):
+        """``(W, H)`` of one member."""
+        K = self.Ks[member]
+        W = np.empty((K, self.V), dtype=np.float64)
+        H = np.empty((self.N, K), dtype=np.float64)
+        _lib.check_batch(self._lib.salnmf_batch_download_member(self._h, int(member), _ptr(W), _ptr(H)))
+        return W, H
+
+    def kl_step(self, n_steps: int, members, n_given):
+        """``n_steps`` joint updates of each listed member (``n_given[i]`` given signatures of ``members[i]``)."""
+        m, g = _ints(members), _ints(n_given)
+        if m.shape != g.shape:
+            raise ValueError("'members' and 'n_given' must have the same length.")
+        _lib.check_batch(self._lib.salnmf_batch_kl_step(self._h, int(n_steps), len(m), _iptr(m), _iptr(g)))
+
+    def objective_async(self, slot: int, members):
+        """Queue the objectives of the listed members into row ``slot`` of the objective array (no host round trip)."""
+        m = _ints(members)
+        _lib.check_batch(self._lib.salnmf_batch_objective_async(self._h, int(slot), len(m), _iptr(m)))
+
+    def objective_read(self, first: int, count: int) -> np.ndarray:
+        """Rows ``[first, first + count)`` of the objective array: ``(count, n_members)``."""
+        out = np.empty((int(count), self.M), dtype=np.float64)
+        _lib.check_batch(self._lib.salnmf_batch_objective_read(self._h, int(first), int(count), out.ctypes.data_as(POINTER(c_double))))
+        return out
+
+    def samplewise_kl(self) -> np.ndarray:
+        """Per-sample KL divergences of every member: ``(n_members, N)``."""
+        out = np.empty((self.M, self.N), dtype=np.float64)
+        _lib.check_batch(self._lib.salnmf_batch_samplewise_kl(self._h, out.ctypes.data_as(POINTER(c_double))))
+        return out

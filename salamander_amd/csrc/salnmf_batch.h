@@ -1,0 +1,35 @@
+// KLNMFSweep on the device (salnmf_batch.hip, include/salnmf.h: salnmf_batch_*): many independent KLNMF models of at most
+// 16 signatures on ONE count matrix, one workgroup per model.
+//
+// Layout (one batch = one device, one X):
+//   X    [Np][96]       shared by all members, clipped and padded as an engine holds it (salnmf_kernels.h)
+//   xlx  [Np][16]       its x-only KL constants (the forward pass's mode 0), once per upload of X
+//   per member m:  W [K_m][V], H [Np][16] (pad columns 0, pad rows 1 -- an engine's H for K <= 16), G [K_m][V] (the last
+//                  step's reduced numerator, what the small kernel leaves behind), objective partials [fgrid] and an arrival
+//                  counter of the in-launch sum
+// The step is the single-model small-cohort kernel's body (salnmf_small.hip: small_kl_body) and the objective / per-sample
+// divergences restate forward_kernel's modes 0 / 1 (salnmf_forward_kernel.h) with the grid an engine of this shape uses:
+// every member gets the bits a single engine computes for it.
+#pragma once
+#include "salnmf_launch.h"
+
+namespace salnmf {
+
+struct BatchMember {
+    double* W;  // [K][V]
+    double* H;  // [Np][16]
+    double* G;  // [K][V]
+    int K;
+};
+
+// one launch of the batched step: workgroup i runs nsteps steps of member active[i] with n_given[i] given signatures
+struct SmallBatchArgs {
+    const double* __restrict__ X;
+    const BatchMember* __restrict__ members;
+    const int* __restrict__ active;   // [n_active]
+    const int* __restrict__ n_given;  // [n_active]
+    int V, ntiles, nsteps;
+};
+int launch_small_kl_batch(const SmallBatchArgs& a, int n_active, hipStream_t stream);
+
+}  // namespace salnmf

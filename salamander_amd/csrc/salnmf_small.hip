@@ -20,6 +20,7 @@
 // (tests/test_gpu_small.py compares them).
 #define SALNMF_TEMPLATES_ONLY 1
 #include "salnmf_launch.h"
+#include "salnmf_batch.h"
 
 namespace salnmf {
 namespace {
@@ -31,12 +32,17 @@ constexpr int SM_ITEMS = 16 * VMAX;    // (k, v) entries of W / G
 
 // MULTI: a wave has more than one tile (only with NG = 4): the H tiles are read and written every step, and a group's
 // slabs fall into two parts.  Otherwise H stays in registers and `part` has one half.
+// doubles of LDS a workgroup of NG groups of four waves uses (the same for every KS)
+template <int NG>
+constexpr int small_lds_doubles() { return 16 * WS + 4 * NG * SM_REGION; }
+
+// The body of one model's n_steps steps, shared by the single-model kernel and the batched one (one model per workgroup):
+// the same instructions, hence the same bits.  `lds` is the workgroup's small_lds_doubles<NG>() doubles.
 template <int KS, int NG, bool MULTI>
-__global__ void __launch_bounds__(256 * NG, 1) small_kl_kernel(SmallParams p) {
+__device__ __forceinline__ void small_kl_body(SmallParams p, double* lds) {
     constexpr int NW = 4 * NG, NT = 64 * NW;
     static_assert(KS <= 4, "n_signatures <= 16: one signature tile");
     static_assert(!MULTI || NG == 4, "several tiles per wave only in the full workgroup");
-    __shared__ __attribute__((aligned(16))) double lds[16 * WS + NW * SM_REGION];
     double* Wl = lds;                // [16][WS], padded as stage_W leaves it; rewritten by the tail of every step
     double* space = lds + 16 * WS;   // the waves' regions; parked tiles, parts and the tail's scratch reuse them
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c16 = lane & 15, q = lane >> 4;
@@ -260,6 +266,29 @@ __global__ void __launch_bounds__(256 * NG, 1) small_kl_kernel(SmallParams p) {
     }
 }
 
+template <int KS, int NG, bool MULTI>
+__global__ void __launch_bounds__(256 * NG, 1) small_kl_kernel(SmallParams p) {
+    __shared__ __attribute__((aligned(16))) double lds[small_lds_doubles<NG>()];
+    small_kl_body<KS, NG, MULTI>(p, lds);
+}
+
+// KLNMFSweep (salnmf_batch.h): workgroup i runs the steps of member a.active[i] -- the single-model kernel's body on that
+// member's W, H and numerator, X shared.  Members of different signature counts share the launch: the contraction depth
+// is picked per workgroup (the branch is uniform), LDS does not depend on it and the registers are those of the widest.
+template <int NG, bool MULTI>
+__global__ void __launch_bounds__(256 * NG, 1) small_kl_batch_kernel(SmallBatchArgs a) {
+    __shared__ __attribute__((aligned(16))) double lds[small_lds_doubles<NG>()];
+    const int m = a.active[blockIdx.x];
+    const BatchMember& b = a.members[m];
+    const SmallParams p{a.X, b.H, b.W, b.W, b.G, a.V, b.K, a.ntiles, a.nsteps, a.n_given[blockIdx.x], 0 /* SALNMF_CLIP_ALL */};
+    if (b.K <= 4)
+        small_kl_body<1, NG, MULTI>(p, lds);
+    else if (b.K <= 8)
+        small_kl_body<2, NG, MULTI>(p, lds);
+    else
+        small_kl_body<4, NG, MULTI>(p, lds);
+}
+
 template <int KS>
 int launch_ks(const SmallParams& p, hipStream_t stream) {
     const int ng = std::min(4, (p.ntiles + 3) / 4);
@@ -278,6 +307,23 @@ int launch_ks(const SmallParams& p, hipStream_t stream) {
 }
 
 }  // namespace
+
+int launch_small_kl_batch(const SmallBatchArgs& a, int n_active, hipStream_t stream) {
+    if (a.ntiles < 1 || a.ntiles > SMALL_MAX_TILES || n_active < 1) return 1;
+    const dim3 g(n_active);
+    switch (std::min(4, (a.ntiles + 3) / 4)) {  // (the single-model launch's choice of NG)
+        case 1: hipLaunchKernelGGL((small_kl_batch_kernel<1, false>), g, dim3(256), 0, stream, a); break;
+        case 2: hipLaunchKernelGGL((small_kl_batch_kernel<2, false>), g, dim3(512), 0, stream, a); break;
+        case 3: hipLaunchKernelGGL((small_kl_batch_kernel<3, false>), g, dim3(768), 0, stream, a); break;
+        default:
+            if (a.ntiles <= 16)
+                hipLaunchKernelGGL((small_kl_batch_kernel<4, false>), g, dim3(1024), 0, stream, a);
+            else
+                hipLaunchKernelGGL((small_kl_batch_kernel<4, true>), g, dim3(1024), 0, stream, a);
+            break;
+    }
+    return 0;
+}
 
 int launch_small_kl_steps(int KS, const SmallParams& p, hipStream_t stream) {
     if (p.ntiles < 1 || p.ntiles > SMALL_MAX_TILES || p.K > 16) return 1;

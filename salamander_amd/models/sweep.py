@@ -1,0 +1,231 @@
+"""``KLNMFSweep``: many KLNMF fits of one count matrix -- a range of signature counts, several seeds -- in one batched run.
+
+The reference's tutorial chooses the number of signatures by fitting one model per candidate, one after another
+(``tutorial.ipynb`` section 1.6)::
+
+    for n_signatures in range(1, 10):
+        model = KLNMF(n_signatures=n_signatures); model.fit(adata.copy())
+
+At the tutorial's size (192 samples x 96 features) one fit keeps one CU busy and the rest of the device idle.  The sweep
+runs the members side by side instead: one workgroup per model, all of them in each launch (``batch.py``,
+``csrc/salnmf_batch.h``).  Every member comes out bit for bit as the fit of the loop above with
+``objective_in_step=False``: the same initialisation (``StandardNMF._initialize`` on the member's own model, in member
+order), the same steps, objectives and convergence tests.  Members the batched kernel cannot run (more than 16 signatures,
+more than 1 024 samples or 96 features, all signatures given) are fitted one after another by ``KLNMF.fit``.
+"""
+
+from __future__ import annotations
+
+import time
+from typing import Any
+
+import numpy as np
+
+from ..anndata_compat import ANNDATA_TYPES
+from ..batch import MAX_FEATURES, MAX_SAMPLES, MAX_SIGNATURES, SLOTS, BatchEngine
+from ..initialization import INIT_METHODS, check_given_asignatures
+from ..utils import type_checker, value_checker
+from .klnmf import KLNMF
+from .signature_nmf import SignatureNMF
+
+
+class KLNMFSweep:
+    """Fit ``KLNMF(K)`` for every K of ``ns_signatures`` and every seed of ``seeds`` on one count matrix.
+
+    ``fit`` returns the models in K-major, seed-minor order; ``reconstruction_errors_`` holds their summed sample-wise
+    KL divergences as ``(len(ns_signatures), max(1, len(seeds)))``, ``batched_`` whether each member ran in the batched
+    kernel (True) or through ``KLNMF.fit`` (False).  Hyperparameters are shared by all members."""
+
+    def __init__(
+        self,
+        ns_signatures=range(1, 10),
+        seeds=None,
+        init_method: str = "nndsvd",
+        min_iterations: int = 500,
+        max_iterations: int = 10000,
+        conv_test_freq: int = 10,
+        tol: float = 1e-7,
+        device: int = 0,
+        device_init: bool = True,
+        distributed: bool = False,
+    ):
+        ns = list(ns_signatures)
+        if not ns or not all(isinstance(k, (int, np.integer)) and not isinstance(k, bool) and k > 0 for k in ns):
+            raise ValueError("'ns_signatures' must be a non-empty collection of positive integers.")
+        if distributed:
+            raise ValueError("A sweep runs on one device: 'distributed=True' is not supported.")
+        value_checker("init_method", init_method, INIT_METHODS)
+        self.ns_signatures = [int(k) for k in ns]
+        self.seeds = None if not seeds else [int(s) for s in seeds]
+        self.init_method = init_method
+        self.min_iterations = min_iterations
+        self.max_iterations = max_iterations
+        self.conv_test_freq = conv_test_freq
+        self.tol = tol
+        self.device = device
+        self.device_init = device_init
+        self.models_: list[KLNMF] = []
+        self.batched_ = np.zeros(0, dtype=bool)
+        self.reconstruction_errors_ = np.zeros((0, 0))
+        self.timings_: dict[str, float] = {}
+        self.member_steps_ = 0
+
+    # ------------------------------------------------------------------ members
+    def _model(self, n_signatures: int) -> KLNMF:
+        return KLNMF(
+            n_signatures, self.init_method, self.min_iterations, self.max_iterations, self.conv_test_freq, self.tol,
+            objective_in_step=False, device=self.device, device_init=self.device_init,
+        )
+
+    def _members(self, init_kwargs):
+        """``(K, init_kwargs of the member)`` in K-major, seed-minor order."""
+        base = {} if init_kwargs is None else dict(init_kwargs)
+        out = []
+        for k in self.ns_signatures:
+            if self.seeds:
+                out.extend((k, base | {"seed": s}) for s in self.seeds)
+            else:
+                out.append((k, init_kwargs))
+        return out
+
+    @staticmethod
+    def _close_engine(model: KLNMF) -> None:
+        if model._engine is not None:
+            model._engine.close()
+            model._engine = None
+        model._resident = set()
+
+    # ------------------------------------------------------------------ fit
+    def fit(self, adata, given_parameters: dict[str, Any] | None = None, init_kwargs: dict[str, Any] | None = None,
+            fitting_kwargs: dict[str, Any] | None = None, history: bool = True) -> list[KLNMF]:
+        type_checker("adata", adata, ANNDATA_TYPES)
+        if fitting_kwargs and (set(fitting_kwargs) - {"weights_kl", "weights_lhalf"} or any(v is not None for v in fitting_kwargs.values())):
+            raise ValueError("A sweep has no weighted step: 'fitting_kwargs' (weights_kl, weights_lhalf) are not supported.")
+        n_given = SignatureNMF._n_given(given_parameters)
+        if given_parameters and "asignatures" in given_parameters:
+            for k in self.ns_signatures:  # (KLNMF.fit's own check, before any member is touched)
+                check_given_asignatures(given_parameters["asignatures"], adata, k)
+        n_obs, n_vars = np.shape(adata.X)
+        members = self._members(init_kwargs)
+        in_reach = [n_obs <= MAX_SAMPLES and n_vars <= MAX_FEATURES and k <= MAX_SIGNATURES and k > n_given for k, _ in members]
+
+        t0 = time.perf_counter()
+        batch_ids = [i for i, ok in enumerate(in_reach) if ok]
+        batch = None
+        if batch_ids:
+            try:
+                batch = BatchEngine(n_obs, n_vars, [members[i][0] for i in batch_ids], device=self.device)
+            except RuntimeError:
+                batch = None  # (a device without the batched kernel: every member takes KLNMF.fit)
+        slot_of = {i: j for j, i in enumerate(batch_ids)} if batch is not None else {}
+        models: list[KLNMF] = []
+        t_init = t_fallback = 0.0
+        try:
+            if batch is not None:
+                batch.upload_X(np.asarray(adata.X, dtype=np.float64), clip=True)
+            # every member in order: initialised (batched) or fitted (fallback) exactly as the tutorial's loop would
+            # do it, so that the legacy NumPy RNG of the random methods advances the same way
+            for i, (k, kwargs) in enumerate(members):
+                model = self._model(k)
+                ta = time.perf_counter()
+                if i in slot_of:
+                    model._setup_adata(adata.copy())  # (the member's own copy, X clipped as fit() leaves it)
+                    model._initialize(given_parameters, kwargs)
+                    model._setup_fitting_parameters(None)
+                    batch.upload_member(slot_of[i], model.asignatures.X, model.adata.obsm["exposures"])
+                    self._close_engine(model)  # (a sweep holds no per-member engine)
+                    t_init += time.perf_counter() - ta
+                else:
+                    model.fit(adata.copy(), given_parameters, kwargs, history=history)
+                    model.compute_reconstruction_errors()
+                    self._close_engine(model)
+                    t_fallback += time.perf_counter() - ta
+                models.append(model)
+            tb = time.perf_counter()
+            steps = 0
+            if batch is not None:
+                n_iters, objectives, steps = self._batched_loop(batch, len(batch_ids), n_given)
+                kl = batch.samplewise_kl()
+                for i, j in slot_of.items():
+                    model = models[i]
+                    W, H = batch.download_member(j)
+                    model.asignatures.X = W
+                    model.adata.obsm["exposures"] = H
+                    model.n_iterations_ = n_iters[j]
+                    if history:
+                        model.history["objective_function"] = objectives[j][1:]
+                    model.adata.obs["reconstruction_error"] = kl[j]
+            t_batched = time.perf_counter() - tb
+        finally:
+            if batch is not None:
+                batch.close()
+        self.models_ = models
+        self.batched_ = np.array([i in slot_of for i in range(len(members))], dtype=bool)
+        cols = max(1, len(self.seeds or []))
+        self.reconstruction_errors_ = np.array([m.reconstruction_error for m in models]).reshape(len(self.ns_signatures), cols)
+        self.member_steps_ = steps
+        self.timings_ = {"total_s": time.perf_counter() - t0, "init_s": t_init, "batched_s": t_batched, "fallback_s": t_fallback}
+        return models
+
+    def _next_stop(self, n_iteration: int) -> int:
+        return SignatureNMF._next_stop(self, n_iteration)  # (reads conv_test_freq and max_iterations only)
+
+    def _batched_loop(self, batch: BatchEngine, n_members: int, n_given: int):
+        """SignatureNMF's fit loop (signature_nmf.py:369-405) for all members at once: the objective at iteration 0 and at
+        every multiple of conv_test_freq, a member stops at its first test with ``rel_change < tol`` from min_iterations
+        on, or at the cap.  Before min_iterations no test can stop anyone: steps and objectives are only queued and read
+        in one go; from there on every test is read.  Returns the members' iteration counts, objective lists and the
+        member-steps run."""
+        freq = self.conv_test_freq
+        objectives: list[list[float]] = [[] for _ in range(n_members)]
+        n_iters = [0] * n_members
+        pending: list[tuple[int, list[int]]] = []  # queued, unread rows of the objective array and their members
+        next_row = 0
+
+        def queue(members):
+            nonlocal next_row
+            if len(pending) == SLOTS:
+                read()
+            batch.objective_async(next_row, members)
+            pending.append((next_row, list(members)))
+            next_row = (next_row + 1) % SLOTS
+
+        def read():
+            while pending:
+                first = pending[0][0]
+                count = 1
+                while count < len(pending) and pending[count][0] == first + count:
+                    count += 1
+                rows = batch.objective_read(first, count)
+                for r in range(count):
+                    for m in pending[r][1]:
+                        objectives[m].append(float(rows[r][m]))
+                del pending[:count]
+
+        active = list(range(n_members))
+        queue(active)
+        n_iteration, steps = 0, 0
+        while active:
+            stop = self._next_stop(n_iteration)
+            batch.kl_step(stop - n_iteration, active, [n_given] * len(active))
+            steps += (stop - n_iteration) * len(active)
+            n_iteration = stop
+            last = n_iteration >= self.max_iterations
+            if n_iteration % freq == 0:
+                queue(active)
+                if not last and n_iteration >= self.min_iterations:
+                    read()
+                    still = []
+                    for m in active:
+                        prev, cur = objectives[m][-2], objectives[m][-1]
+                        if np.abs(prev - cur) / np.abs(prev) < self.tol:
+                            n_iters[m] = n_iteration
+                        else:
+                            still.append(m)
+                    active = still
+            if last:
+                for m in active:
+                    n_iters[m] = n_iteration
+                active = []
+        read()
+        return n_iters, objectives, steps
