@@ -414,8 +414,9 @@ int salnmf_profile_reconstruct(salnmf_engine* e, int n_calls, double* avg_ms);
  * choose the number of signatures (tutorial.ipynb section 1.6: KLNMF(n_signatures=k).fit(adata.copy()) for k = 1..9).
  * Limits: n_features <= 96, n_samples <= 1024 (64 tiles of 16), 1 <= n_signatures <= 16 per member, unweighted.  Every
  * member's W, H and objectives are bit for bit what an engine of that shape computes (salnmf_kl_step,
- * salnmf_objective_async, salnmf_samplewise_kl): the step is the small-cohort kernel's body, the passes restate the forward
- * kernel with the engine's grid (csrc/salnmf_batch.h).  Errors of these entry points: salnmf_batch_last_error. */
+ * salnmf_objective_async, salnmf_samplewise_kl): the step and the passes call the same bodies as the small-cohort kernel
+ * and the forward kernel, with the engine's grid (csrc/salnmf_batch.h).  Errors of these entry points:
+ * salnmf_batch_last_error. */
 typedef struct salnmf_batch salnmf_batch;
 #define SALNMF_BATCH_SLOTS 256 /* rows of the objective array: one row per convergence test, one column per member */
 const char* salnmf_batch_last_error(void);

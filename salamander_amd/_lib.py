@@ -210,10 +210,3 @@ def last_error() -> str:
 def check(rc: int) -> None:
     if rc != 0:
         raise RuntimeError(f"salnmf: {last_error()}")
-
-
-def check_batch(rc: int) -> None:
-    """``check`` for the ``salnmf_batch_*`` entry points, which report through ``salnmf_batch_last_error``."""
-    if rc != 0:
-        msg = load().salnmf_batch_last_error()
-        raise RuntimeError(f"salnmf: {msg.decode() if msg else ''}")

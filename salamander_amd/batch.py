@@ -43,7 +43,7 @@ class BatchEngine:
         self.M = len(self.Ks)
         ks = _ints(self.Ks)
         handle = ctypes.c_void_p()
-        _lib.check_batch(self._lib.salnmf_batch_create(self.device, self.V, self.N, self.M, _iptr(ks), ctypes.byref(handle)))
+        _lib.check(self._lib.salnmf_batch_create(self.device, self.V, self.N, self.M, _iptr(ks), ctypes.byref(handle)))
         self._handle = handle
 
     @property
@@ -66,20 +66,20 @@ class BatchEngine:
 
     def upload_X(self, X, clip: bool = False):
         X = _as_c(X, (self.N, self.V), "X")
-        _lib.check_batch(self._lib.salnmf_batch_upload_X(self._h, _ptr(X), int(bool(clip))))
+        _lib.check(self._lib.salnmf_batch_upload_X(self._h, _ptr(X), int(bool(clip))))
 
     def upload_member(self, member: int, W, H):
         K = self.Ks[member]
         W = _as_c(W, (K, self.V), "W")
         H = _as_c(H, (self.N, K), "H")
-        _lib.check_batch(self._lib.salnmf_batch_upload_member(self._h, int(member), _ptr(W), _ptr(H)))
+        _lib.check(self._lib.salnmf_batch_upload_member(self._h, int(member), _ptr(W), _ptr(H)))
 
     def download_member(self, member: int):
         """``(W, H)`` of one member."""
         K = self.Ks[member]
         W = np.empty((K, self.V), dtype=np.float64)
         H = np.empty((self.N, K), dtype=np.float64)
-        _lib.check_batch(self._lib.salnmf_batch_download_member(self._h, int(member), _ptr(W), _ptr(H)))
+        _lib.check(self._lib.salnmf_batch_download_member(self._h, int(member), _ptr(W), _ptr(H)))
         return W, H
 
     def kl_step(self, n_steps: int, members, n_given):
@@ -87,21 +87,21 @@ class BatchEngine:
         m, g = _ints(members), _ints(n_given)
         if m.shape != g.shape:
             raise ValueError("'members' and 'n_given' must have the same length.")
-        _lib.check_batch(self._lib.salnmf_batch_kl_step(self._h, int(n_steps), len(m), _iptr(m), _iptr(g)))
+        _lib.check(self._lib.salnmf_batch_kl_step(self._h, int(n_steps), len(m), _iptr(m), _iptr(g)))
 
     def objective_async(self, slot: int, members):
         """Queue the objectives of the listed members into row ``slot`` of the objective array (no host round trip)."""
         m = _ints(members)
-        _lib.check_batch(self._lib.salnmf_batch_objective_async(self._h, int(slot), len(m), _iptr(m)))
+        _lib.check(self._lib.salnmf_batch_objective_async(self._h, int(slot), len(m), _iptr(m)))
 
     def objective_read(self, first: int, count: int) -> np.ndarray:
         """Rows ``[first, first + count)`` of the objective array: ``(count, n_members)``."""
         out = np.empty((int(count), self.M), dtype=np.float64)
-        _lib.check_batch(self._lib.salnmf_batch_objective_read(self._h, int(first), int(count), out.ctypes.data_as(POINTER(c_double))))
+        _lib.check(self._lib.salnmf_batch_objective_read(self._h, int(first), int(count), out.ctypes.data_as(POINTER(c_double))))
         return out
 
     def samplewise_kl(self) -> np.ndarray:
         """Per-sample KL divergences of every member: ``(n_members, N)``."""
         out = np.empty((self.M, self.N), dtype=np.float64)
-        _lib.check_batch(self._lib.salnmf_batch_samplewise_kl(self._h, out.ctypes.data_as(POINTER(c_double))))
+        _lib.check(self._lib.salnmf_batch_samplewise_kl(self._h, out.ctypes.data_as(POINTER(c_double))))
         return out

@@ -2,6 +2,7 @@
 // One engine = one GPU = one shard of the sample axis.  All launches go to the
 // engine's own HIP stream; nothing inside a step synchronises with the host.
 #include "../../include/salnmf.h"
+#include "salnmf_error.h"
 #include "salnmf_launch.h"
 #include "salnmf_mv_kernels.h"
 #include "salnmf_mv_wide_kernels.h"
@@ -15,7 +16,6 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -37,18 +37,6 @@ static hipError_t salnmf_poison_malloc(void** p, size_t n) {
 }
 #define hipMalloc(p, n) salnmf_poison_malloc((void**)(p), (n))
 #endif
-
-static thread_local std::string g_err;
-
-static int fail(const char* fmt, ...) {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return 1;
-}
 
 // ---- RCCL is bound at first use, not at load time.  The PyTorch-ROCm wheel ships its own librccl.so (SONAME
 // librccl.so.1, requested by libtorch_hip.so under the unversioned name), the system has /opt/rocm/lib/librccl.so.1.
@@ -119,20 +107,10 @@ static int rccl_bind() {
 #define ncclGroupEnd g_rccl.GroupEnd
 #define ncclGetErrorString g_rccl.GetErrorString
 
-#define HIPCK(call)                                                                              \
-    do {                                                                                         \
-        hipError_t e_ = (call);                                                                  \
-        if (e_ != hipSuccess) return fail("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
 #define NCCLCK(call)                                                                             \
     do {                                                                                         \
         ncclResult_t r_ = (call);                                                                \
         if (r_ != ncclSuccess) return fail("%s failed: %s (%s:%d)", #call, ncclGetErrorString(r_), __FILE__, __LINE__); \
-    } while (0)
-#define CK(call)               \
-    do {                       \
-        int rc_ = (call);      \
-        if (rc_) return rc_;   \
     } while (0)
 
 // up to this many tiles (16 samples each) the one-workgroup multi-step kernel (salnmf_small.hip) beats two launches per
@@ -500,13 +478,16 @@ static int ensure_halt(salnmf_engine* e) {
     return 0;
 }
 
+void salnmf::launch_xlogx_lane(const double* X, int64_t Np, int V, double* c, hipStream_t stream) {
+    hipLaunchKernelGGL(xlogx_lane_kernel, dim3((unsigned)((Np + 15) / 16)), dim3(256), 0, stream, X, Np, V, VMAX, c);
+}
+
 // the x-only part of the KL divergence (salnmf_kernels.h: tile_kl), once per upload of X: the constants per (sample, lane column)
 static int ensure_xlogx(salnmf_engine* e) {
     if (e->xlx_valid) return 0;
     if (!e->xlx) HIPCK(hipMalloc(&e->xlx, (size_t)e->NB * e->Np * 16 * sizeof(double)));
     for (int b = 0; b < e->NB; ++b) {  // (feature blocks: the constants of every block's own features)
-        hipLaunchKernelGGL(xlogx_lane_kernel, dim3((unsigned)((e->Np + 15) / 16)), dim3(256), 0, e->stream, e->X + (size_t)b * e->Np * VMAX, e->Np,
-                           block_width(e, b), VMAX, e->xlx + (size_t)b * e->Np * 16);
+        launch_xlogx_lane(e->X + (size_t)b * e->Np * VMAX, e->Np, block_width(e, b), e->xlx + (size_t)b * e->Np * 16, e->stream);
         HIPCK(hipGetLastError());
     }
     e->xlx_valid = true;
@@ -752,7 +733,7 @@ int salnmf_create(int device, int n_features, int64_t n_samples, int n_signature
     e->KP = e->NC > 1 ? KC : 16 * ((e->KS + 3) / 4);
     int64_t wg_needed = (e->ntiles + WAVES - 1) / WAVES;
     e->grid = (int)std::min<int64_t>(prop.multiProcessorCount, wg_needed);
-    e->fgrid = (int)std::min<int64_t>(2 * prop.multiProcessorCount, wg_needed);
+    e->fgrid = forward_grid(prop.multiProcessorCount, e->ntiles);
     // MvNMF overlaps single-workgroup kernels on a second stream with the passes over the samples.  Workgroups are
     // dealt round-robin to the 8 XCDs and a one-workgroup kernel lands on the first XCD, whichever kernel is
     // dispatched first: leaving one CU per XCD free (3 % of the pass) guarantees it a place

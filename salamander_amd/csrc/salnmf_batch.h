@@ -7,9 +7,9 @@
 //   per member m:  W [K_m][V], H [Np][16] (pad columns 0, pad rows 1 -- an engine's H for K <= 16), G [K_m][V] (the last
 //                  step's reduced numerator, what the small kernel leaves behind), objective partials [fgrid] and an arrival
 //                  counter of the in-launch sum
-// The step is the single-model small-cohort kernel's body (salnmf_small.hip: small_kl_body) and the objective / per-sample
-// divergences restate forward_kernel's modes 0 / 1 (salnmf_forward_kernel.h) with the grid an engine of this shape uses:
-// every member gets the bits a single engine computes for it.
+// The step calls the same body as the single-model small-cohort kernel (salnmf_small.hip: small_kl_body), and the objective /
+// per-sample divergences call the same body as forward_kernel's modes 0 / 1 (salnmf_forward_kernel.h: forward_body) with the
+// grid an engine of this shape uses (forward_grid): every member gets the bits a single engine computes for it.
 #pragma once
 #include "salnmf_launch.h"
 

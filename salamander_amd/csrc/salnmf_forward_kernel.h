@@ -43,12 +43,14 @@ struct FwdParams {
 template <int KS>
 constexpr int fwd_lds_doubles() { return 4 * KS * WS + WAVES * Geo<KS>::HL + BLOCK + Geo<KS>::KP + LOGTAB_DOUBLES; }
 
-template <int KS, int MODE, bool PIN = false>
-__global__ void __launch_bounds__(BLOCK, (fwd_lds_doubles<KS>() * 8 <= 80 * 1024 ? 2 : 1)) forward_kernel(FwdParams p) {
+// The pass on lds[fwd_lds_doubles<KS>()]: the body of forward_kernel below and of the sweep's batch_forward_kernel
+// (salnmf_batch.hip), which runs it for one model per workgroup.  p by value: taken by reference, the parameters are read
+// through the kernel's copy of its argument and forward_kernel<13, 1, true> spilled 24 bytes per lane.
+template <int KS, int MODE, bool PIN>
+__device__ __forceinline__ void forward_body(FwdParams p, double* lds) {
     using G_ = Geo<KS>;
     constexpr int KP = G_::KP, LS = G_::LS, HV = G_::HV;
     constexpr int FROWS = 4 * KS;  // rows of W read by the P product
-    __shared__ __attribute__((aligned(16))) double lds[fwd_lds_doubles<KS>()];  // <= 80 KB (two per CU) up to KS = 13
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -245,6 +247,12 @@ __global__ void __launch_bounds__(BLOCK, (fwd_lds_doubles<KS>() * 8 <= 80 * 1024
             }
         }
     }
+}
+
+template <int KS, int MODE, bool PIN = false>
+__global__ void __launch_bounds__(BLOCK, (fwd_lds_doubles<KS>() * 8 <= 80 * 1024 ? 2 : 1)) forward_kernel(FwdParams p) {
+    __shared__ __attribute__((aligned(16))) double lds[fwd_lds_doubles<KS>()];  // <= 80 KB (two per CU) up to KS = 13
+    forward_body<KS, MODE, PIN>(p, lds);
 }
 
 }  // namespace salnmf

@@ -5,6 +5,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 #include "salnmf_kernels.h"
 #include "salnmf_kernels_f32.h"
 
@@ -27,6 +29,12 @@ int launch_fused_inst(const FusedSel& s, const FusedParams& p, int grid, hipStre
 // (mode + FWD_PIN: the instantiation whose P starts from p.pin -- modes 0, 1, 2, 4)
 constexpr int FWD_PIN = 16;
 int launch_forward_inst(int KS, int mode, const FwdParams& p, int grid, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop);
+// Workgroups of the forward pass over ntiles tiles on cus CUs: two per CU, no more than the tiles fill.  This fixes the
+// objective's summation order (partials per workgroup), so whatever must reproduce an engine's objective takes it from here.
+inline int forward_grid(int cus, int64_t ntiles) { return (int)std::min<int64_t>(2 * cus, (ntiles + WAVES - 1) / WAVES); }
+
+// xlogx_lane_kernel (salnmf_plain_kernels.h, compiled into salnmf.hip) over X [Np][VMAX] -> c [Np][16]
+void launch_xlogx_lane(const double* X, int64_t Np, int V, double* c, hipStream_t stream);
 
 // Small cohorts (salnmf_small.hip): n_steps joint KL steps of an unweighted problem with at most SMALL_MAX_TILES tiles and
 // 16 signatures in ONE one-workgroup launch; same bits as the per-step path.  0 = launched, 1 = shape not covered.

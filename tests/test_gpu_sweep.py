@@ -2,8 +2,8 @@
 
 Member (K, s) is compared with ``KLNMF(K, ..., objective_in_step=False).fit(adata.copy(), given, init_kwargs | {"seed": s})``
 by ``np.array_equal`` / list equality: signatures, exposures, objective history, iteration count and per-sample
-reconstruction errors (``csrc/salnmf_batch.h``: the step is the single-model small-cohort kernel's body, the objective and
-per-sample passes restate the forward kernel with the engine's grid)."""
+reconstruction errors (``csrc/salnmf_batch.h``: the step calls the same body as the single-model small-cohort kernel, the
+objective and per-sample passes call the same body as the forward kernel, with the engine's grid)."""
 import os
 
 import numpy as np
