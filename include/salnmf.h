@@ -409,7 +409,7 @@ int salnmf_profile_objective(salnmf_engine* e, int n_calls, double* avg_ms);
 int salnmf_profile_reconstruct(salnmf_engine* e, int n_calls, double* avg_ms);
 
 /* ---- Batched sweeps (KLNMFSweep, salamander_amd/models/sweep.py): many independent KLNMF models -- different
- * n_signatures, different initialisations -- on ONE count matrix, one workgroup per model, every model's step, objective
+ * n_signatures, different initialisations -- on ONE count matrix or on bootstrap resamples of it (below), one workgroup per model, every model's step, objective
  * and per-sample divergences in one launch for all of them.  What the reference's tutorial does one fit after another to
  * choose the number of signatures (tutorial.ipynb section 1.6: KLNMF(n_signatures=k).fit(adata.copy()) for k = 1..9).
  * Limits: n_features <= 96, n_samples <= 1024 (64 tiles of 16), 1 <= n_signatures <= 16 per member, unweighted.  Every
@@ -442,6 +442,34 @@ int salnmf_batch_objective_async(salnmf_batch* b, int slot, int n_active, const 
 int salnmf_batch_objective_read(salnmf_batch* b, int first, int count, double* out);
 /* samplewise_kl_divergence (_utils_klnmf.py:58-97) of every member -> out (n_members x n_samples). */
 int salnmf_batch_samplewise_kl(salnmf_batch* b, double* out);
+
+/* ---- Bootstrap resamples of a count matrix, drawn on the device (csrc/salnmf_resample.h).  X (n_samples x n_features) holds
+ * non-negative integer values with row totals T_n < 2^32.  Row n of resample r is one multinomial draw of T_n trials with
+ * probabilities X[n, :] / T_n, built as T_n categorical draws:
+ *   generator: Philox4x32-10 (Salmon et al., Random123), key = (seed & 0xffffffff, seed >> 32);
+ *   block q of row n of resample r: counter (q mod 2^32, q >> 32, n, r) -> words (o0, o1, o2, o3);
+ *   draw 2q uses u = o0 | o1 << 32, draw 2q + 1 uses u = o2 | o3 << 32; draws j >= T_n are discarded;
+ *   t = floor(u T_n / 2^64); the draw lands in the smallest v with cum[v] > t, cum[v] = sum_{w <= v} X[n, w].
+ * Integer arithmetic throughout: the same bits on every run, row totals kept, zero cells stay zero, and resample r does not
+ * depend on n_resamples.  The bias of a draw against the exact probabilities is at most T_n / 2^64.  Both entry points
+ * refuse, before any launch, a negative or non-integer entry and a row total >= 2^32 (status 1, salnmf_last_error names the
+ * row); 1 <= n_resamples <= 65535. */
+/* Stand-alone: upload, draw, download.  n_features <= 3072.  out: n_resamples x n_samples x n_features, plain counts. */
+int salnmf_resample_counts(int device, const double* X, int64_t n_samples, int n_features, int n_resamples, uint64_t seed,
+                           double* out);
+/* n_resamples resamples of the batch's uploaded X (salnmf_batch_upload_X first), drawn device to device into slots in X's
+ * own layout -- pad rows and columns 0, entries max(count, SALNMF_EPSILON) as upload_X(clip = 1) leaves them -- each with its
+ * x log x constants.  "Dataset" r is slot r, dataset -1 the uploaded X.  A second call, or another upload of X, drops the
+ * slots and puts every member back on dataset -1. */
+int salnmf_batch_resample(salnmf_batch* b, int n_resamples, uint64_t seed);
+/* The dataset a member's steps, objectives and per-sample divergences read from now on (-1 at creation). */
+int salnmf_batch_set_dataset(salnmf_batch* b, int member, int dataset);
+/* raw == 0: the dataset as n_samples x n_features; a resample comes back as plain counts (the clipped zeros restored to 0),
+ * dataset -1 as the device holds it.  raw != 0: the slot as the kernels read it, 16 ceil(n_samples / 16) x 96. */
+int salnmf_batch_download_dataset(salnmf_batch* b, int dataset, int raw, double* out);
+/* Development aid (tools/bench_bootstrap.py): salnmf_batch_resample once, then n_calls launches of the resample kernel
+ * alone between two events -> average milliseconds per launch.  The slots hold the same resamples afterwards. */
+int salnmf_profile_resample(salnmf_batch* b, int n_resamples, uint64_t seed, int n_calls, double* avg_ms);
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,7 @@ from . import models
 from ._lib import EngineUnavailable
 from .anndata_compat import AnnData, MuData
 from .engine import Engine
+from .resample import resample_counts
 
 __version__ = "0.1.0"
-__all__ = ["models", "Engine", "AnnData", "MuData", "EngineUnavailable"]
+__all__ = ["models", "Engine", "AnnData", "MuData", "EngineUnavailable", "resample_counts"]

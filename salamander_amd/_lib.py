@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_int, c_int64, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_int, c_int64, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (SALNMF_LIB: a development hook of this loader -- tools/ A/B runs of two builds of the library in one gpurun call)
@@ -115,6 +115,12 @@ SIGNATURES = {
     "salnmf_batch_objective_async": (c_int, [_P, c_int, c_int, POINTER(c_int)]),
     "salnmf_batch_objective_read": (c_int, [_P, c_int, c_int, _D]),
     "salnmf_batch_samplewise_kl": (c_int, [_P, _D]),
+    # bootstrap resamples: salamander_amd/resample.py, batch.py
+    "salnmf_resample_counts": (c_int, [c_int, _D, c_int64, c_int, c_int, c_uint64, _D]),
+    "salnmf_batch_resample": (c_int, [_P, c_int, c_uint64]),
+    "salnmf_batch_set_dataset": (c_int, [_P, c_int, c_int]),
+    "salnmf_batch_download_dataset": (c_int, [_P, c_int, c_int, _D]),
+    "salnmf_profile_resample": (c_int, [_P, c_int, c_uint64, c_int, _D]),
 }
 
 OBJECTIVE_SLOTS = 256  # SALNMF_OBJECTIVE_SLOTS

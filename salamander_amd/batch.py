@@ -14,6 +14,7 @@ import numpy as np
 
 from . import _lib
 from .engine import _as_c, _ptr
+from .resample import check_n_resamples, check_seed
 
 SLOTS = _lib.BATCH_SLOTS
 MAX_SAMPLES = 1024  # 64 tiles of 16 samples (the small-cohort kernel's reach)
@@ -30,7 +31,7 @@ def _iptr(a):
 
 
 class BatchEngine:
-    """Device-resident state of a sweep: X once, W / H / numerator per member."""
+    """Device-resident state of a sweep: X once, bootstrap resamples of it on request, W / H / numerator per member."""
 
     def __init__(self, n_samples: int, n_features: int, n_signatures, device: int = 0):
         self._lib = _lib.load()
@@ -45,6 +46,7 @@ class BatchEngine:
         handle = ctypes.c_void_p()
         _lib.check(self._lib.salnmf_batch_create(self.device, self.V, self.N, self.M, _iptr(ks), ctypes.byref(handle)))
         self._handle = handle
+        self.R = 0  # resamples of X on the device
 
     @property
     def _h(self):
@@ -67,6 +69,34 @@ class BatchEngine:
     def upload_X(self, X, clip: bool = False):
         X = _as_c(X, (self.N, self.V), "X")
         _lib.check(self._lib.salnmf_batch_upload_X(self._h, _ptr(X), int(bool(clip))))
+        self.R = 0  # (the resamples go with the X they were drawn from)
+
+    def resample(self, n_resamples: int, seed: int = 0):
+        """Draw ``n_resamples`` bootstrap resamples of the uploaded X on the device (``resample.py``): datasets
+        ``0 .. n_resamples - 1`` of this batch, dataset -1 being X itself.  Every member is back on dataset -1."""
+        R, seed = check_n_resamples(n_resamples), check_seed(seed)
+        self.R = 0
+        _lib.check(self._lib.salnmf_batch_resample(self._h, R, seed))
+        self.R = R
+
+    def set_dataset(self, member: int, dataset: int):
+        """The matrix ``member`` fits from now on: resample ``dataset``, or -1 for the uploaded X (the default)."""
+        _lib.check(self._lib.salnmf_batch_set_dataset(self._h, int(member), int(dataset)))
+
+    def download_dataset(self, dataset: int, raw: bool = False) -> np.ndarray:
+        """A dataset as ``(N, V)`` -- a resample as plain counts, dataset -1 as the device holds it -- or, with ``raw``,
+        the slot as the kernels read it: ``(16 * ceil(N / 16), 96)``, padded with zeros, entries clipped to EPSILON."""
+        shape = (16 * ((self.N + 15) // 16), MAX_FEATURES) if raw else (self.N, self.V)
+        out = np.empty(shape, dtype=np.float64)
+        _lib.check(self._lib.salnmf_batch_download_dataset(self._h, int(dataset), int(bool(raw)), _ptr(out)))
+        return out
+
+    def profile_resample(self, n_resamples: int, seed: int = 0, n_calls: int = 20) -> float:
+        """Development aid: average milliseconds of the resample kernel alone, by device events."""
+        ms = c_double(0.0)
+        _lib.check(self._lib.salnmf_profile_resample(self._h, check_n_resamples(n_resamples), check_seed(seed), int(n_calls), ctypes.byref(ms)))
+        self.R = int(n_resamples)
+        return float(ms.value)
 
     def upload_member(self, member: int, W, H):
         K = self.Ks[member]

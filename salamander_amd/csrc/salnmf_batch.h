@@ -1,9 +1,12 @@
 // KLNMFSweep on the device (salnmf_batch.hip, include/salnmf.h: salnmf_batch_*): many independent KLNMF models of at most
-// 16 signatures on ONE count matrix, one workgroup per model.
+// 16 signatures on ONE count matrix or on bootstrap resamples of it, one workgroup per model.
 //
-// Layout (one batch = one device, one X):
-//   X    [Np][96]       shared by all members, clipped and padded as an engine holds it (salnmf_kernels.h)
+// Layout (one batch = one device, one uploaded X and R >= 0 resamples of it, "datasets" -1 and 0 .. R - 1):
+//   X    [Np][96]       the uploaded matrix, clipped and padded as an engine holds it (salnmf_kernels.h)
 //   xlx  [Np][16]       its x-only KL constants (the forward pass's mode 0), once per upload of X
+//   Xr   [R][Np][96], xlxr [R][Np][16]   the resamples in the same layout (salnmf_resample.h writes them in place)
+//   every member reads ONE dataset, through the X / xlx pointers of its BatchMember (the uploaded X until
+//   salnmf_batch_set_dataset says otherwise)
 //   per member m:  W [K_m][V], H [Np][16] (pad columns 0, pad rows 1 -- an engine's H for K <= 16), G [K_m][V] (the last
 //                  step's reduced numerator, what the small kernel leaves behind), objective partials [fgrid] and an arrival
 //                  counter of the in-launch sum
@@ -20,11 +23,12 @@ struct BatchMember {
     double* H;  // [Np][16]
     double* G;  // [K][V]
     int K;
+    const double* X;    // [Np][96] the member's dataset
+    const double* xlx;  // [Np][16] and its constants
 };
 
 // one launch of the batched step: workgroup i runs nsteps steps of member active[i] with n_given[i] given signatures
 struct SmallBatchArgs {
-    const double* __restrict__ X;
     const BatchMember* __restrict__ members;
     const int* __restrict__ active;   // [n_active]
     const int* __restrict__ n_given;  // [n_active]

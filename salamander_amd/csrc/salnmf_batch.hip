@@ -5,6 +5,7 @@
 #include "../../include/salnmf.h"
 #include "salnmf_batch.h"
 #include "salnmf_error.h"
+#include "salnmf_resample.h"
 
 #include <algorithm>
 #include <string>
@@ -18,8 +19,6 @@ namespace {
 // one launch of the batched forward pass: blockIdx.y = entry of `active`, blockIdx.x = the workgroup of that member's
 // pass (gridDim.x = the engine's forward_grid for this shape)
 struct BatchFwdArgs {
-    const double* __restrict__ X;
-    const double* __restrict__ xlx;     // [Np][16] (mode 0)
     const BatchMember* __restrict__ members;
     const int* __restrict__ active;
     double* out;                        // mode 0: [n_members][gridDim.x] workgroup partials; mode 1: [n_members][Np]
@@ -31,8 +30,9 @@ struct BatchFwdArgs {
 
 // forward_body<KS, MODE> (salnmf_forward_kernel.h) for one member with the parameters an engine of <= 16 signatures and
 // <= 96 features passes for salnmf_objective_async (mode 0, the in-launch sum) and salnmf_samplewise_kl (mode 1):
-// unweighted, no pending exposure scale, one feature block, one signature chunk.  Members of 1-4, 5-8 and 9-16 signatures
-// share the launch (KS = 1, 2, 4; the branch is uniform per workgroup, LDS is sized for the widest).
+// the member's own dataset, unweighted, no pending exposure scale, one feature block, one signature chunk.  Members of
+// 1-4, 5-8 and 9-16 signatures share the launch (KS = 1, 2, 4; the branch is uniform per workgroup, LDS is sized for the
+// widest).
 template <int MODE>
 __global__ void __launch_bounds__(BLOCK, 2) batch_forward_kernel(BatchFwdArgs a) {
     static_assert(fwd_lds_doubles<4>() * 8 <= 80 * 1024, "two workgroups per CU, as forward_kernel at KS <= 4");
@@ -40,10 +40,10 @@ __global__ void __launch_bounds__(BLOCK, 2) batch_forward_kernel(BatchFwdArgs a)
     const int m = a.active[blockIdx.y];
     const BatchMember& b = a.members[m];
     FwdParams p{};
-    p.X = a.X;
+    p.X = b.X;
     p.H = b.H;
     p.W = b.W;
-    p.xlx = a.xlx;
+    p.xlx = b.xlx;  // [Np][16] (mode 0)
     p.out = a.out + (MODE == 0 ? (size_t)m * gridDim.x : (size_t)m * 16 * a.ntiles);
     p.N = a.N;
     p.V = p.ldw = a.V;
@@ -80,7 +80,64 @@ struct salnmf_batch {
     std::vector<hipEvent_t> ev;             // per slot: completion of the launch that wrote it
     std::vector<char> queued;
     bool x_ok = false;
+    // bootstrap resamples of X (salnmf_batch_resample): R slots in X's layout, the counts they were drawn from, and the
+    // dataset each member reads (-1: the uploaded X); the device's member table is rewritten before the next launch
+    std::vector<double> hostX;  // [N][V] as uploaded, unclipped
+    double *Xr = nullptr, *xlxr = nullptr;
+    int R = 0;
+    std::vector<int> dataset;
+    bool members_dirty = false;
 };
+
+// the device's member table follows the host's once the launches that read the old one are done
+static int flush_members(salnmf_batch* b) {
+    if (!b->members_dirty) return 0;
+    HIPCK(hipStreamSynchronize(b->stream));
+    HIPCK(hipMemcpy(b->dmembers, b->members.data(), b->members.size() * sizeof(BatchMember), hipMemcpyHostToDevice));
+    b->members_dirty = false;
+    return 0;
+}
+
+static void point_member(salnmf_batch* b, int m, int dataset) {
+    BatchMember& mb = b->members[(size_t)m];
+    mb.X = dataset < 0 ? b->X : b->Xr + (size_t)dataset * b->Np * VMAX;
+    mb.xlx = dataset < 0 ? b->xlx : b->xlxr + (size_t)dataset * b->Np * 16;
+    b->dataset[(size_t)m] = dataset;
+    b->members_dirty = true;
+}
+
+// the resamples go with the X they were drawn from: every member is back on the uploaded X
+static void drop_resamples(salnmf_batch* b) {
+    for (int m = 0; m < b->M; ++m)
+        if (b->dataset[(size_t)m] >= 0) point_member(b, m, -1);
+    if (b->Xr) (void)hipFree(b->Xr);
+    if (b->xlxr) (void)hipFree(b->xlxr);
+    b->Xr = b->xlxr = nullptr;
+    b->R = 0;
+}
+
+// Counts a resample can be drawn from: integer values, none negative, row totals below 2^32.  The counts as uint32.
+static int check_counts(const double* X, int64_t N, int V, std::vector<uint32_t>& counts) {
+    counts.resize((size_t)N * V);
+    for (int64_t n = 0; n < N; ++n) {
+        uint64_t total = 0;
+        for (int v = 0; v < V; ++v) {
+            const double x = X[(size_t)n * V + v];
+            if (!(x >= 0.0) || x >= 4294967296.0 || x != (double)(uint64_t)x)
+                return fail("resampling needs non-negative integer counts below 2^32: row %lld, column %d holds %g", (long long)n, v, x);
+            total += (uint64_t)x;
+            counts[(size_t)n * V + v] = (uint32_t)x;
+        }
+        if (total >> 32) return fail("resampling needs row totals below 2^32: row %lld sums to %llu", (long long)n, (unsigned long long)total);
+    }
+    return 0;
+}
+
+static int check_resample_args(int n_resamples) {
+    // (one workgroup per (row, resample): the resample is the grid's y)
+    if (n_resamples < 1 || n_resamples > 65535) return fail("n_resamples must be in [1, 65535], got %d", n_resamples);
+    return 0;
+}
 
 static int check_member(const salnmf_batch* b, int m) {
     if (!b) return fail("null batch");
@@ -140,6 +197,7 @@ int salnmf_batch_create(int device, int n_features, int64_t n_samples, int n_mem
     b->Np = 16 * b->ntiles;
     b->fgrid = forward_grid(prop.multiProcessorCount, b->ntiles);
     b->K.assign(n_signatures, n_signatures + n_members);
+    b->dataset.assign((size_t)n_members, -1);
     auto cleanup = [&](int rc) {
         salnmf_batch_destroy(b);
         return rc;
@@ -163,7 +221,7 @@ int salnmf_batch_create(int device, int n_features, int64_t n_samples, int n_mem
         if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return cleanup(fail("event create failed"));
     double *W = b->state, *G = b->state + kv, *H = b->state + 2 * kv;
     for (int m = 0; m < n_members; ++m) {
-        b->members.push_back(BatchMember{W, H, G, b->K[(size_t)m]});
+        b->members.push_back(BatchMember{W, H, G, b->K[(size_t)m], b->X, b->xlx});
         W += (size_t)b->K[(size_t)m] * b->V;
         G += (size_t)b->K[(size_t)m] * b->V;
         H += hsz;
@@ -181,7 +239,7 @@ void salnmf_batch_destroy(salnmf_batch* b) {
     if (b->stream) (void)hipStreamSynchronize(b->stream);
     for (hipEvent_t e : b->ev)
         if (e) (void)hipEventDestroy(e);
-    for (void* p : {(void*)b->X, (void*)b->xlx, (void*)b->state, (void*)b->part, (void*)b->klout, (void*)b->counter, (void*)b->dmembers, (void*)b->dstep,
+    for (void* p : {(void*)b->X, (void*)b->xlx, (void*)b->Xr, (void*)b->xlxr, (void*)b->state, (void*)b->part, (void*)b->klout, (void*)b->counter, (void*)b->dmembers, (void*)b->dstep,
                     (void*)b->dobj})
         if (p) (void)hipFree(p);
     if (b->pin) (void)hipHostFree(b->pin);
@@ -201,6 +259,8 @@ int salnmf_batch_upload_X(salnmf_batch* b, const double* X, int clip) {
             host[(size_t)n * VMAX + v] = x;
         }
     HIPCK(hipStreamSynchronize(b->stream));
+    drop_resamples(b);
+    b->hostX.assign(X, X + (size_t)b->N * b->V);
     HIPCK(hipMemcpyAsync(b->X, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice, b->stream));
     launch_xlogx_lane(b->X, b->Np, b->V, b->xlx, b->stream);
     HIPCK(hipGetLastError());
@@ -257,7 +317,8 @@ int salnmf_batch_kl_step(salnmf_batch* b, int n_steps, int n_active, const int* 
         want.push_back(n_given[i]);
     }
     CK(set_list(b, b->dstep, b->step_list, want));
-    SmallBatchArgs a{b->X, b->dmembers, b->dstep, b->dstep + n_active, b->V, (int)b->ntiles, 0};
+    CK(flush_members(b));
+    SmallBatchArgs a{b->dmembers, b->dstep, b->dstep + n_active, b->V, (int)b->ntiles, 0};
     constexpr int kMaxPerLaunch = 4096;  // (salnmf_kl_step's bound on one launch of the small kernel)
     for (int i = 0; i < n_steps; i += a.nsteps) {
         a.nsteps = std::min(kMaxPerLaunch, n_steps - i);
@@ -276,7 +337,8 @@ int salnmf_batch_objective_async(salnmf_batch* b, int slot, int n_active, const 
     b->queued[(size_t)slot] = 1;
     if (n_active > 0) {
         CK(set_list(b, b->dobj, b->obj_list, std::vector<int>(members, members + n_active)));
-        BatchFwdArgs a{b->X, b->xlx, b->dmembers, b->dobj, b->part, b->counter, b->pin + (size_t)slot * b->M, b->N, b->ntiles, b->V};
+        CK(flush_members(b));
+        BatchFwdArgs a{b->dmembers, b->dobj, b->part, b->counter, b->pin + (size_t)slot * b->M, b->N, b->ntiles, b->V};
         hipLaunchKernelGGL(batch_forward_kernel<0>, dim3(b->fgrid, n_active), dim3(BLOCK), 0, b->stream, a);
         HIPCK(hipGetLastError());
     }
@@ -303,7 +365,8 @@ int salnmf_batch_samplewise_kl(salnmf_batch* b, double* out) {
     std::vector<int> all((size_t)b->M);
     for (int m = 0; m < b->M; ++m) all[(size_t)m] = m;
     CK(set_list(b, b->dobj, b->obj_list, all));
-    BatchFwdArgs a{b->X, b->xlx, b->dmembers, b->dobj, b->klout, nullptr, nullptr, b->N, b->ntiles, b->V};
+    CK(flush_members(b));
+    BatchFwdArgs a{b->dmembers, b->dobj, b->klout, nullptr, nullptr, b->N, b->ntiles, b->V};
     hipLaunchKernelGGL(batch_forward_kernel<1>, dim3(b->fgrid, b->M), dim3(BLOCK), 0, b->stream, a);
     HIPCK(hipGetLastError());
     std::vector<double> host((size_t)b->M * b->Np);
@@ -311,6 +374,128 @@ int salnmf_batch_samplewise_kl(salnmf_batch* b, double* out) {
     HIPCK(hipStreamSynchronize(b->stream));
     for (int m = 0; m < b->M; ++m) std::copy(host.begin() + (size_t)m * b->Np, host.begin() + (size_t)m * b->Np + b->N, out + (size_t)m * b->N);
     return 0;
+}
+
+int salnmf_batch_resample(salnmf_batch* b, int n_resamples, uint64_t seed) {
+    if (!b) return fail("null batch");
+    if (!b->x_ok) return fail("upload X first");
+    CK(check_resample_args(n_resamples));
+    std::vector<uint32_t> counts;
+    CK(check_counts(b->hostX.data(), b->N, b->V, counts));
+    HIPCK(hipSetDevice(b->device));
+    HIPCK(hipStreamSynchronize(b->stream));
+    drop_resamples(b);
+    uint32_t* dcounts = nullptr;
+    auto cleanup = [&](int rc) {
+        if (dcounts) (void)hipFree(dcounts);
+        if (rc) drop_resamples(b);
+        return rc;
+    };
+    const size_t xsz = (size_t)b->Np * VMAX, csz = (size_t)b->Np * 16;
+    if (hipMalloc(&b->Xr, (size_t)n_resamples * xsz * sizeof(double)) != hipSuccess || hipMalloc(&b->xlxr, (size_t)n_resamples * csz * sizeof(double)) != hipSuccess ||
+        hipMalloc(&dcounts, counts.size() * sizeof(uint32_t)) != hipSuccess)
+        return cleanup(fail("hipMalloc failed (%d resamples)", n_resamples));
+    b->R = n_resamples;
+    if (hipMemcpyAsync(dcounts, counts.data(), counts.size() * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream) != hipSuccess)
+        return cleanup(fail("hipMemcpy failed"));
+    // straight into the slots, in X's layout: pad rows and columns 0, the N x V block clipped as upload_X(clip = 1) clips
+    launch_resample(ResampleArgs{dcounts, b->Xr, b->N, b->Np, b->V, VMAX, (uint32_t)seed, (uint32_t)(seed >> 32), SALNMF_EPSILON}, n_resamples, b->stream);
+    if (hipGetLastError() != hipSuccess) return cleanup(fail("resample launch failed"));
+    for (int r = 0; r < n_resamples; ++r) {
+        launch_xlogx_lane(b->Xr + (size_t)r * xsz, b->Np, b->V, b->xlxr + (size_t)r * csz, b->stream);
+        if (hipGetLastError() != hipSuccess) return cleanup(fail("xlogx launch failed"));
+    }
+    if (hipStreamSynchronize(b->stream) != hipSuccess) return cleanup(fail("resample failed on the device"));
+    return cleanup(0);
+}
+
+int salnmf_batch_set_dataset(salnmf_batch* b, int member, int dataset) {
+    CK(check_member(b, member));
+    if (dataset < -1 || dataset >= b->R) return fail("dataset %d out of range (%d resamples; -1 is the uploaded X)", dataset, b->R);
+    if (b->dataset[(size_t)member] != dataset) point_member(b, member, dataset);
+    return 0;
+}
+
+int salnmf_batch_download_dataset(salnmf_batch* b, int dataset, int raw, double* out) {
+    if (!b || !out) return fail("null argument");
+    if (!b->x_ok) return fail("upload X first");
+    if (dataset < -1 || dataset >= b->R) return fail("dataset %d out of range (%d resamples; -1 is the uploaded X)", dataset, b->R);
+    HIPCK(hipSetDevice(b->device));
+    const double* src = dataset < 0 ? b->X : b->Xr + (size_t)dataset * b->Np * VMAX;
+    if (raw) {
+        HIPCK(hipMemcpyAsync(out, src, (size_t)b->Np * VMAX * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+        HIPCK(hipStreamSynchronize(b->stream));
+        return 0;
+    }
+    std::vector<double> host((size_t)b->N * VMAX);
+    HIPCK(hipMemcpyAsync(host.data(), src, host.size() * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    HIPCK(hipStreamSynchronize(b->stream));
+    for (int64_t n = 0; n < b->N; ++n)
+        for (int v = 0; v < b->V; ++v) {
+            const double x = host[(size_t)n * VMAX + v];
+            out[(size_t)n * b->V + v] = dataset >= 0 && x < 0.5 ? 0.0 : x;  // (a resample holds max(count, EPSILON))
+        }
+    return 0;
+}
+
+int salnmf_resample_counts(int device, const double* X, int64_t n_samples, int n_features, int n_resamples, uint64_t seed, double* out) {
+    if (!X || !out) return fail("null argument");
+    if (n_samples < 1 || n_samples > 0x7fffffff) return fail("n_samples must be in [1, 2^31), got %lld", (long long)n_samples);
+    if (n_features < 1 || n_features > RESAMPLE_VMAX) return fail("n_features must be in [1, %d], got %d", RESAMPLE_VMAX, n_features);
+    CK(check_resample_args(n_resamples));
+    std::vector<uint32_t> counts;
+    CK(check_counts(X, n_samples, n_features, counts));
+    int ndev = 0;
+    HIPCK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail("device %d out of range (%d visible)", device, ndev);
+    HIPCK(hipSetDevice(device));
+    hipDeviceProp_t prop;
+    HIPCK(hipGetDeviceProperties(&prop, device));
+    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0) return fail("this build targets gfx950 only; device %d is %s", device, prop.gcnArchName);
+    uint32_t* dcounts = nullptr;
+    double* dout = nullptr;
+    auto cleanup = [&](int rc) {
+        if (dcounts) (void)hipFree(dcounts);
+        if (dout) (void)hipFree(dout);
+        return rc;
+    };
+    const size_t nout = (size_t)n_resamples * counts.size();
+    if (hipMalloc(&dcounts, counts.size() * sizeof(uint32_t)) != hipSuccess || hipMalloc(&dout, nout * sizeof(double)) != hipSuccess)
+        return cleanup(fail("hipMalloc failed (%d resamples of %lld x %d)", n_resamples, (long long)n_samples, n_features));
+    if (hipMemcpy(dcounts, counts.data(), counts.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return cleanup(fail("hipMemcpy failed"));
+    launch_resample(ResampleArgs{dcounts, dout, n_samples, n_samples, n_features, n_features, (uint32_t)seed, (uint32_t)(seed >> 32), 0.0}, n_resamples, nullptr);
+    if (hipGetLastError() != hipSuccess) return cleanup(fail("resample launch failed"));
+    if (hipMemcpy(out, dout, nout * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return cleanup(fail("resample failed on the device"));
+    return cleanup(0);
+}
+
+int salnmf_profile_resample(salnmf_batch* b, int n_resamples, uint64_t seed, int n_calls, double* avg_ms) {
+    if (!b || !avg_ms) return fail("null argument");
+    if (!b->x_ok) return fail("upload X first");
+    if (n_calls < 1) return fail("n_calls must be positive");
+    CK(salnmf_batch_resample(b, n_resamples, seed));  // (validates, allocates the slots, warms the kernel up)
+    std::vector<uint32_t> counts;
+    CK(check_counts(b->hostX.data(), b->N, b->V, counts));
+    uint32_t* dcounts = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto cleanup = [&](int rc) {
+        if (dcounts) (void)hipFree(dcounts);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        return rc;
+    };
+    if (hipMalloc(&dcounts, counts.size() * sizeof(uint32_t)) != hipSuccess || hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)
+        return cleanup(fail("hipMalloc failed"));
+    if (hipMemcpy(dcounts, counts.data(), counts.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return cleanup(fail("hipMemcpy failed"));
+    const ResampleArgs a{dcounts, b->Xr, b->N, b->Np, b->V, VMAX, (uint32_t)seed, (uint32_t)(seed >> 32), SALNMF_EPSILON};
+    (void)hipEventRecord(e0, b->stream);
+    for (int i = 0; i < n_calls; ++i) launch_resample(a, n_resamples, b->stream);  // (the same bits every time)
+    (void)hipEventRecord(e1, b->stream);
+    if (hipGetLastError() != hipSuccess || hipEventSynchronize(e1) != hipSuccess) return cleanup(fail("resample failed on the device"));
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    *avg_ms = (double)ms / n_calls;
+    return cleanup(0);
 }
 
 }  // extern "C"

@@ -273,14 +273,14 @@ __global__ void __launch_bounds__(256 * NG, 1) small_kl_kernel(SmallParams p) {
 }
 
 // KLNMFSweep (salnmf_batch.h): workgroup i runs the steps of member a.active[i] -- the single-model kernel's body on that
-// member's W, H and numerator, X shared.  Members of different signature counts share the launch: the contraction depth
+// member's W, H, numerator and dataset.  Members of different signature counts share the launch: the contraction depth
 // is picked per workgroup (the branch is uniform), LDS does not depend on it and the registers are those of the widest.
 template <int NG, bool MULTI>
 __global__ void __launch_bounds__(256 * NG, 1) small_kl_batch_kernel(SmallBatchArgs a) {
     __shared__ __attribute__((aligned(16))) double lds[small_lds_doubles<NG>()];
     const int m = a.active[blockIdx.x];
     const BatchMember& b = a.members[m];
-    const SmallParams p{a.X, b.H, b.W, b.W, b.G, a.V, b.K, a.ntiles, a.nsteps, a.n_given[blockIdx.x], 0 /* SALNMF_CLIP_ALL */};
+    const SmallParams p{b.X, b.H, b.W, b.W, b.G, a.V, b.K, a.ntiles, a.nsteps, a.n_given[blockIdx.x], 0 /* SALNMF_CLIP_ALL */};
     if (b.K <= 4)
         small_kl_body<1, NG, MULTI>(p, lds);
     else if (b.K <= 8)

@@ -12,6 +12,11 @@ runs the members side by side instead: one workgroup per model, all of them in e
 ``objective_in_step=False``: the same initialisation (``StandardNMF._initialize`` on the member's own model, in member
 order), the same steps, objectives and convergence tests.  Members the batched kernel cannot run (more than 16 signatures,
 more than 1 024 samples or 96 features, all signatures given) are fitted one after another by ``KLNMF.fit``.
+
+``n_resamples=R`` adds bootstrap resamples of the counts as a third axis: the R matrices are drawn once on the device
+(``resample.py``: each sample's mutations redrawn from its own observed spectrum, bit-reproducible from ``resample_seed``),
+member (K, seed, r) fits resample r, and every member still equals the single fit on its matrix bit for bit.  What the
+field does with such fits -- keep the largest K whose signatures come back the same -- is left to the caller.
 """
 
 from __future__ import annotations
@@ -24,6 +29,7 @@ import numpy as np
 from ..anndata_compat import ANNDATA_TYPES
 from ..batch import MAX_FEATURES, MAX_SAMPLES, MAX_SIGNATURES, SLOTS, BatchEngine
 from ..initialization import INIT_METHODS, check_given_asignatures
+from ..resample import check_counts, check_n_resamples, check_seed, resample_counts
 from ..utils import type_checker, value_checker
 from .klnmf import KLNMF
 from .signature_nmf import SignatureNMF
@@ -34,7 +40,13 @@ class KLNMFSweep:
 
     ``fit`` returns the models in K-major, seed-minor order; ``reconstruction_errors_`` holds their summed sample-wise
     KL divergences as ``(len(ns_signatures), max(1, len(seeds)))``, ``batched_`` whether each member ran in the batched
-    kernel (True) or through ``KLNMF.fit`` (False).  Hyperparameters are shared by all members."""
+    kernel (True) or through ``KLNMF.fit`` (False).  Hyperparameters are shared by all members.
+
+    With ``n_resamples = R >= 1`` the members are K-major, seed-middle, resample-minor and member (K, seed, r) fits
+    ``resamples_[r]``, the r-th bootstrap resample of the counts (the same R matrices for every K and seed, drawn from
+    ``resample_seed``).  ``resamples_`` is ``(R, N, V)``, ``resample_of_`` holds r per member (-1 without resamples) and
+    ``reconstruction_errors_`` is ``(len(ns_signatures), max(1, len(seeds)), R)``.  The counts must be non-negative
+    integer values with row totals below 2**32."""
 
     def __init__(
         self,
@@ -48,6 +60,8 @@ class KLNMFSweep:
         device: int = 0,
         device_init: bool = True,
         distributed: bool = False,
+        n_resamples: int = 0,
+        resample_seed: int = 0,
     ):
         ns = list(ns_signatures)
         if not ns or not all(isinstance(k, (int, np.integer)) and not isinstance(k, bool) and k > 0 for k in ns):
@@ -55,6 +69,8 @@ class KLNMFSweep:
         if distributed:
             raise ValueError("A sweep runs on one device: 'distributed=True' is not supported.")
         value_checker("init_method", init_method, INIT_METHODS)
+        self.n_resamples = check_n_resamples(n_resamples, minimum=0)
+        self.resample_seed = check_seed(resample_seed)
         self.ns_signatures = [int(k) for k in ns]
         self.seeds = None if not seeds else [int(s) for s in seeds]
         self.init_method = init_method
@@ -67,6 +83,8 @@ class KLNMFSweep:
         self.models_: list[KLNMF] = []
         self.batched_ = np.zeros(0, dtype=bool)
         self.reconstruction_errors_ = np.zeros((0, 0))
+        self.resamples_ = None
+        self.resample_of_ = np.zeros(0, dtype=int)
         self.timings_: dict[str, float] = {}
         self.member_steps_ = 0
 
@@ -78,15 +96,21 @@ class KLNMFSweep:
         )
 
     def _members(self, init_kwargs):
-        """``(K, init_kwargs of the member)`` in K-major, seed-minor order."""
+        """``(K, init_kwargs of the member, resample of the member or -1)`` in K-major, seed-middle, resample-minor order."""
         base = {} if init_kwargs is None else dict(init_kwargs)
+        resamples = range(self.n_resamples) if self.n_resamples else [-1]
         out = []
         for k in self.ns_signatures:
-            if self.seeds:
-                out.extend((k, base | {"seed": s}) for s in self.seeds)
-            else:
-                out.append((k, init_kwargs))
+            for kwargs in [base | {"seed": s} for s in self.seeds] if self.seeds else [init_kwargs]:
+                out.extend((k, kwargs, r) for r in resamples)
         return out
+
+    def _member_adata(self, adata, r: int):
+        """The member's own copy of the data: the caller's, or resample r under the caller's obs / var names."""
+        own = adata.copy()
+        if r >= 0:
+            own.X = self.resamples_[r].copy()
+        return own
 
     @staticmethod
     def _close_engine(model: KLNMF) -> None:
@@ -106,8 +130,10 @@ class KLNMFSweep:
             for k in self.ns_signatures:  # (KLNMF.fit's own check, before any member is touched)
                 check_given_asignatures(given_parameters["asignatures"], adata, k)
         n_obs, n_vars = np.shape(adata.X)
+        R = self.n_resamples
+        counts = check_counts(adata.X) if R else None  # (before anything touches the device)
         members = self._members(init_kwargs)
-        in_reach = [n_obs <= MAX_SAMPLES and n_vars <= MAX_FEATURES and k <= MAX_SIGNATURES and k > n_given for k, _ in members]
+        in_reach = [n_obs <= MAX_SAMPLES and n_vars <= MAX_FEATURES and k <= MAX_SIGNATURES and k > n_given for k, _, _ in members]
 
         t0 = time.perf_counter()
         batch_ids = [i for i, ok in enumerate(in_reach) if ok]
@@ -119,24 +145,36 @@ class KLNMFSweep:
                 batch = None  # (a device without the batched kernel: every member takes KLNMF.fit)
         slot_of = {i: j for j, i in enumerate(batch_ids)} if batch is not None else {}
         models: list[KLNMF] = []
-        t_init = t_fallback = 0.0
+        t_init = t_fallback = t_resample = 0.0
+        self.resamples_ = None
         try:
             if batch is not None:
                 batch.upload_X(np.asarray(adata.X, dtype=np.float64), clip=True)
+            if R:
+                # the R matrices, once: drawn into the batch's own slots, or stand-alone when there is no batch
+                ta = time.perf_counter()
+                if batch is not None:
+                    batch.resample(R, self.resample_seed)
+                    self.resamples_ = np.stack([batch.download_dataset(r) for r in range(R)])
+                    for i, j in slot_of.items():
+                        batch.set_dataset(j, members[i][2])
+                else:
+                    self.resamples_ = resample_counts(counts, R, self.resample_seed, device=self.device)
+                t_resample = time.perf_counter() - ta
             # every member in order: initialised (batched) or fitted (fallback) exactly as the tutorial's loop would
             # do it, so that the legacy NumPy RNG of the random methods advances the same way
-            for i, (k, kwargs) in enumerate(members):
+            for i, (k, kwargs, r) in enumerate(members):
                 model = self._model(k)
                 ta = time.perf_counter()
                 if i in slot_of:
-                    model._setup_adata(adata.copy())  # (the member's own copy, X clipped as fit() leaves it)
+                    model._setup_adata(self._member_adata(adata, r))  # (the member's own copy, X clipped as fit() leaves it)
                     model._initialize(given_parameters, kwargs)
                     model._setup_fitting_parameters(None)
                     batch.upload_member(slot_of[i], model.asignatures.X, model.adata.obsm["exposures"])
                     self._close_engine(model)  # (a sweep holds no per-member engine)
                     t_init += time.perf_counter() - ta
                 else:
-                    model.fit(adata.copy(), given_parameters, kwargs, history=history)
+                    model.fit(self._member_adata(adata, r), given_parameters, kwargs, history=history)
                     model.compute_reconstruction_errors()
                     self._close_engine(model)
                     t_fallback += time.perf_counter() - ta
@@ -162,9 +200,12 @@ class KLNMFSweep:
         self.models_ = models
         self.batched_ = np.array([i in slot_of for i in range(len(members))], dtype=bool)
         cols = max(1, len(self.seeds or []))
-        self.reconstruction_errors_ = np.array([m.reconstruction_error for m in models]).reshape(len(self.ns_signatures), cols)
+        shape = (len(self.ns_signatures), cols, R) if R else (len(self.ns_signatures), cols)
+        self.reconstruction_errors_ = np.array([m.reconstruction_error for m in models]).reshape(shape)
+        self.resample_of_ = np.array([r for _, _, r in members], dtype=int)
         self.member_steps_ = steps
-        self.timings_ = {"total_s": time.perf_counter() - t0, "init_s": t_init, "batched_s": t_batched, "fallback_s": t_fallback}
+        self.timings_ = {"total_s": time.perf_counter() - t0, "init_s": t_init, "batched_s": t_batched, "fallback_s": t_fallback,
+                         "resample_s": t_resample}
         return models
 
     def _next_stop(self, n_iteration: int) -> int:
