@@ -176,7 +176,10 @@ int salnmf_mv_step(salnmf_engine* e, int n_steps, int n_given, double lam, doubl
 /* The pieces of the W step as the reference exposes them (function-level API of mvnmf.py):
  *   salnmf_mv_logdet                  volume_logdet (mvnmf.py:19-24) of the resident W
  *   salnmf_mv_update_W_unconstrained  update_W_unconstrained (:37-66) from the resident (X, W, H) -> Wunc_out [K][V];
- *                                     the resident state is not changed
+ *                                     the resident state is not changed.  Accuracy: the reference's closed-form root
+ *                                     subtracts root - b, so an entry with b = rowsum_H - 4 lam A > 0 is good to
+ *                                     eps * kappa only, kappa ~ rowsum_H^2 / (4 lam B G) (1e6 .. 1e12 on count data); that
+ *                                     is a property of mvnmf.py's formula, which this library restates operation for operation
  *   salnmf_mv_line_search             line_search (:69-92) from the resident (X, W, H) with the caller's
  *                                     W_unconstrained [K][V]: leaves the accepted W and the rescaled H resident, updates gamma */
 int salnmf_mv_logdet(salnmf_engine* e, double delta, double* out);
