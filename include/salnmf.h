@@ -474,6 +474,35 @@ int salnmf_batch_download_dataset(salnmf_batch* b, int dataset, int raw, double*
  * alone between two events -> average milliseconds per launch.  The slots hold the same resamples afterwards. */
 int salnmf_profile_resample(salnmf_batch* b, int n_resamples, uint64_t seed, int n_calls, double* avg_ms);
 
+/* ---- Signature stability: match, cluster and score the signatures of many fits (csrc/salnmf_stability.h, DESIGN.md
+ * section 12 "Stability").  A group is M >= 2 signature matrices of one shape K x V (K <= 16, V <= 96) and one error value
+ * per member (errors == NULL: all zero).  Per group: rows are scaled to unit Euclidean norm; the member of smallest error
+ * (lowest index on ties) provides the first centroids; each round assigns every member's rows to the centroids by the
+ * optimal assignment under the cost 1 - cosine, sums the rows of each cluster over the members in ascending order, and stops
+ * when no assignment changed (the first round always counts as changed) or after max_rounds rounds; otherwise the normalised
+ * sums are the next centroids.  Silhouettes under the cosine distance follow from the cluster sums.
+ * One launch handles all groups.  With T the number of listed members over all groups, in group order, and G = n_groups,
+ * the outputs are padded to 16 signatures and 96 features:
+ *   assignments  T x 16 (row of the member assigned to cluster j; entries j >= K hold j)
+ *   a, b, silhouette  T x 16 (point j of a member is its row assigned to cluster j: mean distance to its own cluster without
+ *                itself, smallest mean distance to another cluster, (b - a) / max(a, b); for K = 1, b is NaN and the
+ *                silhouette 1; entries j >= K are 0)
+ *   n_rounds, converged  G;  consensus  G x 16 x 96 (cluster sums scaled to row sum 1);  cluster_stability  G x 16 (mean
+ *                silhouette of a cluster over the members);  stability  G x 2 (mean and minimum of cluster_stability)
+ *   kernel_ms    NULL, or one double: the launch's milliseconds by device events.
+ * Arguments are validated before any launch (a NaN among the errors is refused too); errors: salnmf_batch_last_error. */
+/* In place: group g lists members[group_offsets[g] .. group_offsets[g + 1]) of the batch (group_offsets: n_groups + 1 values
+ * from 0), all of one n_signatures; the kernel reads the members' W where the steps left it.  errors: one per listed member. */
+int salnmf_batch_stability(salnmf_batch* b, int n_groups, const int* group_offsets, const int* members, const double* errors,
+                           int max_rounds, int* assignments, int* n_rounds, int* converged, double* consensus, double* a,
+                           double* b_dist, double* silhouette, double* cluster_stability, double* stability, double* kernel_ms);
+/* Stand-alone: signatures is T x 16 x 96, zero padded, group after group (n_members[g] matrices of n_signatures[g] rows
+ * and n_features columns each).  Also refused: a row that is not finite or has norm zero. */
+int salnmf_signature_stability(int device, const double* signatures, int n_groups, const int* n_signatures,
+                               const int* n_members, int n_features, const double* errors, int max_rounds, int* assignments,
+                               int* n_rounds, int* converged, double* consensus, double* a, double* b_dist, double* silhouette,
+                               double* cluster_stability, double* stability, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

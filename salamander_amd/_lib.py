@@ -28,6 +28,7 @@ CORR_SIGNATURE_SCALINGS, CORR_SAMPLE_SCALINGS, CORR_SIGNATURE_EMBEDDINGS, CORR_S
 # every symbol include/salnmf.h declares: name -> (restype, argtypes)
 _P = c_void_p
 _D = POINTER(c_double)
+_I = POINTER(c_int)
 SIGNATURES = {
     "salnmf_last_error": (c_char_p, []),
     "salnmf_version": (c_int, []),
@@ -121,6 +122,9 @@ SIGNATURES = {
     "salnmf_batch_set_dataset": (c_int, [_P, c_int, c_int]),
     "salnmf_batch_download_dataset": (c_int, [_P, c_int, c_int, _D]),
     "salnmf_profile_resample": (c_int, [_P, c_int, c_uint64, c_int, _D]),
+    # signature stability: salamander_amd/stability.py, batch.py
+    "salnmf_batch_stability": (c_int, [_P, c_int, _I, _I, _D, c_int, _I, _I, _I, _D, _D, _D, _D, _D, _D, _D]),
+    "salnmf_signature_stability": (c_int, [c_int, _D, c_int, _I, _I, c_int, _D, c_int, _I, _I, _I, _D, _D, _D, _D, _D, _D, _D]),
 }
 
 OBJECTIVE_SLOTS = 256  # SALNMF_OBJECTIVE_SLOTS

@@ -15,6 +15,7 @@ import numpy as np
 from . import _lib
 from .engine import _as_c, _ptr
 from .resample import check_n_resamples, check_seed
+from .stability import _Outputs, check_errors, check_group_shape, check_max_rounds
 
 SLOTS = _lib.BATCH_SLOTS
 MAX_SAMPLES = 1024  # 64 tiles of 16 samples (the small-cohort kernel's reach)
@@ -135,3 +136,32 @@ class BatchEngine:
         out = np.empty((self.M, self.N), dtype=np.float64)
         _lib.check(self._lib.salnmf_batch_samplewise_kl(self._h, out.ctypes.data_as(POINTER(c_double))))
         return out
+
+    def stability(self, groups, errors=None, max_rounds: int = 20):
+        """Match, cluster and score the signatures of the listed members where they lie on the device (``stability.py``).
+
+        ``groups`` is a list of lists of member indices, each list of one number of signatures and at least two members;
+        ``errors`` one sequence per group with one value per member (None: all zero).  One launch for all groups; returns
+        one ``StabilityResult`` per group.  ``ValueError`` before any launch for a group that mixes numbers of signatures
+        or has fewer than two members."""
+        groups = [[int(m) for m in g] for g in groups]
+        max_rounds = check_max_rounds(max_rounds)
+        if not groups:
+            raise ValueError("'groups' must hold at least one group.")
+        shapes = []
+        for g in groups:
+            if any(not 0 <= m < self.M for m in g):
+                raise ValueError(f"A group lists a member outside 0 .. {self.M - 1}.")
+            ks = {self.Ks[m] for m in g}
+            if len(ks) > 1:
+                raise ValueError(f"The members of one group must share their number of signatures, got {sorted(ks)}.")
+            check_group_shape(len(g), ks.pop() if ks else 1, self.V)
+            shapes.append((len(g), self.Ks[g[0]]))
+        errs = check_errors(errors, shapes)
+        offsets = _ints(np.concatenate([[0], np.cumsum([len(g) for g in groups])]))
+        members = _ints([m for g in groups for m in g])
+        out = _Outputs(shapes)
+        _lib.check(self._lib.salnmf_batch_stability(
+            self._h, len(groups), _iptr(offsets), _iptr(members), None if errs is None else _ptr(errs), max_rounds, *out.pointers(),
+        ))
+        return out.results(self.V)

@@ -1,13 +1,16 @@
 // KLNMFSweep on the device: the batch handle of include/salnmf.h (salnmf_batch_*), the batched objective / per-sample
 // divergence passes, and the host side of the batched step (its kernel: salnmf_small.hip, small_kl_batch_kernel).
-// Layout and the bit-for-bit argument: salnmf_batch.h, DESIGN.md section 12.
+// Layout and the bit-for-bit argument: salnmf_batch.h, DESIGN.md section 12.  Also the host side of the bootstrap resampler
+// (salnmf_resample.h) and of the signature-stability kernel (salnmf_stability.h).
 #define SALNMF_TEMPLATES_ONLY 1
 #include "../../include/salnmf.h"
 #include "salnmf_batch.h"
 #include "salnmf_error.h"
 #include "salnmf_resample.h"
+#include "salnmf_stability.h"
 
 #include <algorithm>
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -166,6 +169,120 @@ static int set_list(salnmf_batch* b, int* dev, std::vector<int>& cache, const st
     cache = want;
     return 0;
 }
+
+// ---- signature stability (salnmf_stability.h): the two feeders share everything after their own validation
+namespace {
+
+struct StabOut {
+    int *assignments, *n_rounds, *converged;
+    double *consensus, *a, *b, *silhouette, *cluster, *stability, *kernel_ms;
+};
+
+// (the destructor waits for the stream first: on an early return no pending copy outlives a buffer, host or device)
+struct DevBufs {
+    hipStream_t stream;
+    std::vector<void*> ptrs;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    explicit DevBufs(hipStream_t s) : stream(s) {}
+    ~DevBufs() {
+        (void)hipStreamSynchronize(stream);
+        for (void* p : ptrs) (void)hipFree(p);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+    template <typename T>
+    T* get(size_t n) {
+        void* p = nullptr;
+        if (hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return nullptr;
+        ptrs.push_back(p);
+        return (T*)p;
+    }
+};
+
+int check_stab_out(const StabOut& o) {
+    if (!o.assignments || !o.n_rounds || !o.converged || !o.consensus || !o.a || !o.b || !o.silhouette || !o.cluster || !o.stability)
+        return fail("null output");
+    return 0;
+}
+
+// K, M of one group and the launch as a whole (one workgroup per group: the group is the grid's x)
+int check_stab_group(int g, int K, int M) {
+    if (K < 1 || K > STAB_K) return fail("group %d: n_signatures must be in [1, %d], got %d", g, STAB_K, K);
+    if (M < 2) return fail("group %d: a group needs at least 2 members, got %d", g, M);
+    return 0;
+}
+
+// One launch over all groups, then the results: per listed member [16] (assignments, a, b, silhouette), per group
+// [16][96] (consensus), [16] (cluster stability), [2] (mean, minimum) and the round count / converged flag.
+int run_stability(hipStream_t stream, const std::vector<StabGroup>& groups, const std::vector<const double*>& src, int ld, int V, const double* errors,
+                  int max_rounds, const StabOut& o) {
+    const size_t G = groups.size(), T = src.size();
+    // (host buffers of the asynchronous copies: declared before d, so they outlive its wait for the stream)
+    std::vector<double> err(T, 0.0), abz(3 * T * STAB_K), score(2 * G);
+    std::vector<int> rounds(2 * G);
+    if (errors) {
+        err.assign(errors, errors + T);
+        for (size_t t = 0; t < T; ++t)
+            if (std::isnan(err[t])) return fail("errors must not hold NaNs (listed member %zu)", t);
+    }
+    DevBufs d(stream);
+    StabArgs a{};
+    StabGroup* dgroups = d.get<StabGroup>(G);
+    const double** dsrc = d.get<const double*>(T);
+    double* derr = d.get<double>(T);
+    a.u = d.get<double>(T * STAB_K * VMAX);
+    a.xx = d.get<double>(T * STAB_K);
+    a.assign = d.get<int>(T * STAB_K);
+    a.a = d.get<double>(3 * T * STAB_K);
+    a.consensus = d.get<double>(G * STAB_K * VMAX);
+    a.cluster = d.get<double>(G * STAB_K);
+    a.score = d.get<double>(2 * G);
+    a.rounds = d.get<int>(2 * G);
+    if (!dgroups || !dsrc || !derr || !a.u || !a.xx || !a.assign || !a.a || !a.consensus || !a.cluster || !a.score || !a.rounds)
+        return fail("hipMalloc failed (stability of %zu members in %zu groups)", T, G);
+    a.b = a.a + T * STAB_K;
+    a.sil = a.b + T * STAB_K;
+    a.groups = dgroups;
+    a.src = dsrc;
+    a.err = derr;
+    a.ld = ld;
+    a.V = V;
+    a.max_rounds = max_rounds;
+    HIPCK(hipMemcpyAsync(dgroups, groups.data(), G * sizeof(StabGroup), hipMemcpyHostToDevice, stream));
+    HIPCK(hipMemcpyAsync(dsrc, src.data(), T * sizeof(double*), hipMemcpyHostToDevice, stream));
+    HIPCK(hipMemcpyAsync(derr, err.data(), T * sizeof(double), hipMemcpyHostToDevice, stream));
+    if (o.kernel_ms) {
+        HIPCK(hipEventCreate(&d.e0));
+        HIPCK(hipEventCreate(&d.e1));
+        HIPCK(hipEventRecord(d.e0, stream));
+    }
+    launch_stability(a, (int)G, stream);
+    HIPCK(hipGetLastError());
+    if (o.kernel_ms) HIPCK(hipEventRecord(d.e1, stream));
+    HIPCK(hipMemcpyAsync(o.assignments, a.assign, T * STAB_K * sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIPCK(hipMemcpyAsync(abz.data(), a.a, abz.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIPCK(hipMemcpyAsync(o.consensus, a.consensus, G * STAB_K * VMAX * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIPCK(hipMemcpyAsync(o.cluster, a.cluster, G * STAB_K * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIPCK(hipMemcpyAsync(score.data(), a.score, score.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIPCK(hipMemcpyAsync(rounds.data(), a.rounds, rounds.size() * sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIPCK(hipStreamSynchronize(stream));
+    std::copy(abz.begin(), abz.begin() + T * STAB_K, o.a);
+    std::copy(abz.begin() + T * STAB_K, abz.begin() + 2 * T * STAB_K, o.b);
+    std::copy(abz.begin() + 2 * T * STAB_K, abz.end(), o.silhouette);
+    std::copy(score.begin(), score.end(), o.stability);
+    for (size_t g = 0; g < G; ++g) {
+        o.n_rounds[g] = rounds[2 * g];
+        o.converged[g] = rounds[2 * g + 1];
+    }
+    if (o.kernel_ms) {
+        float ms = 0.f;
+        HIPCK(hipEventElapsedTime(&ms, d.e0, d.e1));
+        *o.kernel_ms = (double)ms;
+    }
+    return 0;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -496,6 +613,79 @@ int salnmf_profile_resample(salnmf_batch* b, int n_resamples, uint64_t seed, int
     (void)hipEventElapsedTime(&ms, e0, e1);
     *avg_ms = (double)ms / n_calls;
     return cleanup(0);
+}
+
+int salnmf_batch_stability(salnmf_batch* b, int n_groups, const int* group_offsets, const int* members, const double* errors, int max_rounds,
+                           int* assignments, int* n_rounds, int* converged, double* consensus, double* a, double* b_dist, double* silhouette,
+                           double* cluster_stability, double* stability, double* kernel_ms) {
+    if (!b) return fail("null batch");
+    const StabOut o{assignments, n_rounds, converged, consensus, a, b_dist, silhouette, cluster_stability, stability, kernel_ms};
+    CK(check_stab_out(o));
+    if (n_groups < 1 || !group_offsets || !members) return fail("stability needs at least one group");
+    if (max_rounds < 1) return fail("max_rounds must be positive, got %d", max_rounds);
+    if (group_offsets[0] != 0) return fail("group_offsets must start at 0");
+    if (b->V < 1 || b->V > VMAX) return fail("n_features must be in [1, %d], got %d", VMAX, b->V);
+    std::vector<StabGroup> groups;
+    std::vector<const double*> src;
+    for (int g = 0; g < n_groups; ++g) {
+        const int first = group_offsets[g], M = group_offsets[g + 1] - first;
+        if (M < 0) return fail("group_offsets must not decrease (group %d)", g);
+        for (int i = first; i < first + M; ++i) CK(check_member(b, members[i]));
+        const int K = M > 0 ? b->K[(size_t)members[first]] : 1;
+        CK(check_stab_group(g, K, M));
+        for (int i = first; i < first + M; ++i) {
+            if (b->K[(size_t)members[i]] != K)
+                return fail("group %d mixes members of %d and %d signatures (members %d and %d)", g, K, b->K[(size_t)members[i]], members[first], members[i]);
+            src.push_back(b->members[(size_t)members[i]].W);
+        }
+        groups.push_back(StabGroup{K, M, first});
+    }
+    HIPCK(hipSetDevice(b->device));
+    return run_stability(b->stream, groups, src, b->V, b->V, errors, max_rounds, o);
+}
+
+int salnmf_signature_stability(int device, const double* signatures, int n_groups, const int* n_signatures, const int* n_members, int n_features,
+                               const double* errors, int max_rounds, int* assignments, int* n_rounds, int* converged, double* consensus, double* a,
+                               double* b_dist, double* silhouette, double* cluster_stability, double* stability, double* kernel_ms) {
+    const StabOut o{assignments, n_rounds, converged, consensus, a, b_dist, silhouette, cluster_stability, stability, kernel_ms};
+    CK(check_stab_out(o));
+    if (!signatures || n_groups < 1 || !n_signatures || !n_members) return fail("stability needs at least one group");
+    if (n_features < 1 || n_features > VMAX) return fail("n_features must be in [1, %d], got %d", VMAX, n_features);
+    if (max_rounds < 1) return fail("max_rounds must be positive, got %d", max_rounds);
+    std::vector<StabGroup> groups;
+    size_t T = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        CK(check_stab_group(g, n_signatures[g], n_members[g]));
+        for (int m = 0; m < n_members[g]; ++m)
+            for (int k = 0; k < n_signatures[g]; ++k) {
+                const double* row = signatures + ((T + (size_t)m) * STAB_K + (size_t)k) * VMAX;
+                double ss = 0.0;
+                for (int v = 0; v < n_features; ++v) ss += row[v] * row[v];
+                if (!std::isfinite(ss) || !(ss > 0.0))
+                    return fail("group %d, member %d, signature %d: every signature needs finite entries and a positive norm", g, m, k);
+            }
+        groups.push_back(StabGroup{n_signatures[g], n_members[g], (int)T});
+        T += (size_t)n_members[g];
+    }
+    int ndev = 0;
+    HIPCK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail("device %d out of range (%d visible)", device, ndev);
+    HIPCK(hipSetDevice(device));
+    hipDeviceProp_t prop;
+    HIPCK(hipGetDeviceProperties(&prop, device));
+    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0) return fail("this build targets gfx950 only; device %d is %s", device, prop.gcnArchName);
+    double* dsig = nullptr;
+    const size_t n = T * STAB_K * VMAX;
+    if (hipMalloc(&dsig, n * sizeof(double)) != hipSuccess) return fail("hipMalloc failed (%zu signature matrices)", T);
+    int rc = 0;
+    if (hipMemcpy(dsig, signatures, n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = fail("hipMemcpy failed");
+    if (!rc) {
+        std::vector<const double*> src(T);
+        for (size_t t = 0; t < T; ++t) src[t] = dsig + t * STAB_K * VMAX;
+        rc = run_stability(nullptr, groups, src, VMAX, n_features, errors, max_rounds, o);
+    }
+    (void)hipFree(dsig);
+    return rc;
 }
 
 }  // extern "C"

@@ -16,7 +16,9 @@ more than 1 024 samples or 96 features, all signatures given) are fitted one aft
 ``n_resamples=R`` adds bootstrap resamples of the counts as a third axis: the R matrices are drawn once on the device
 (``resample.py``: each sample's mutations redrawn from its own observed spectrum, bit-reproducible from ``resample_seed``),
 member (K, seed, r) fits resample r, and every member still equals the single fit on its matrix bit for bit.  What the
-field does with such fits -- keep the largest K whose signatures come back the same -- is left to the caller.
+field does with such fits -- keep the largest K whose signatures come back the same -- is ``stability=True``: for every K
+the signatures of all its members are matched to each other, clustered into consensus signatures and scored by their
+silhouettes on the device (``stability.py``), and ``suggest_n_signatures`` applies the customary thresholds.
 """
 
 from __future__ import annotations
@@ -30,6 +32,9 @@ from ..anndata_compat import ANNDATA_TYPES
 from ..batch import MAX_FEATURES, MAX_SAMPLES, MAX_SIGNATURES, SLOTS, BatchEngine
 from ..initialization import INIT_METHODS, check_given_asignatures
 from ..resample import check_counts, check_n_resamples, check_seed, resample_counts
+from ..stability import MAX_FEATURES as STABILITY_MAX_FEATURES
+from ..stability import MAX_SIGNATURES as STABILITY_MAX_SIGNATURES
+from ..stability import check_max_rounds, signature_stability
 from ..utils import type_checker, value_checker
 from .klnmf import KLNMF
 from .signature_nmf import SignatureNMF
@@ -46,7 +51,17 @@ class KLNMFSweep:
     ``resamples_[r]``, the r-th bootstrap resample of the counts (the same R matrices for every K and seed, drawn from
     ``resample_seed``).  ``resamples_`` is ``(R, N, V)``, ``resample_of_`` holds r per member (-1 without resamples) and
     ``reconstruction_errors_`` is ``(len(ns_signatures), max(1, len(seeds)), R)``.  The counts must be non-negative
-    integer values with row totals below 2**32."""
+    integer values with row totals below 2**32.
+
+    With ``stability=True`` (every K needs at least two members: seeds x resamples) the members of each K form one group
+    whose signatures are matched, clustered and scored after the fits, in one launch over all K, members in sweep order,
+    the anchor of a group being its member of smallest summed reconstruction error: ``stability_mean_`` and
+    ``stability_min_`` ``(len(ns_signatures),)`` and, one entry per K, ``cluster_stability_ (K,)``,
+    ``consensus_signatures_ (K, V)``, ``assignments_ (M, K)``, ``silhouettes_ (M, K)``, ``stability_rounds_`` and
+    ``stability_converged_``; ``timings_["stability_s"]`` is the time it took.  A K the kernel cannot take (more than 16
+    signatures, or more than 96 features) gets NaN scores, ``None`` for its arrays, 0 rounds and ``False``.
+    ``suggest_n_signatures`` picks the largest K that passes the thresholds; it raises ``ValueError`` on a sweep built
+    without ``stability=True`` and returns ``None`` before ``fit`` (the scores are NaN until then)."""
 
     def __init__(
         self,
@@ -62,6 +77,8 @@ class KLNMFSweep:
         distributed: bool = False,
         n_resamples: int = 0,
         resample_seed: int = 0,
+        stability: bool = False,
+        stability_max_rounds: int = 20,
     ):
         ns = list(ns_signatures)
         if not ns or not all(isinstance(k, (int, np.integer)) and not isinstance(k, bool) and k > 0 for k in ns):
@@ -73,6 +90,10 @@ class KLNMFSweep:
         self.resample_seed = check_seed(resample_seed)
         self.ns_signatures = [int(k) for k in ns]
         self.seeds = None if not seeds else [int(s) for s in seeds]
+        self.stability = bool(stability)
+        self.stability_max_rounds = check_max_rounds(stability_max_rounds)
+        if self.stability and max(1, len(self.seeds or [])) * max(1, self.n_resamples) < 2:
+            raise ValueError("'stability=True' needs at least two members per number of signatures: several seeds, or n_resamples >= 2.")
         self.init_method = init_method
         self.min_iterations = min_iterations
         self.max_iterations = max_iterations
@@ -87,6 +108,7 @@ class KLNMFSweep:
         self.resample_of_ = np.zeros(0, dtype=int)
         self.timings_: dict[str, float] = {}
         self.member_steps_ = 0
+        self._clear_stability()
 
     # ------------------------------------------------------------------ members
     def _model(self, n_signatures: int) -> KLNMF:
@@ -119,6 +141,48 @@ class KLNMFSweep:
             model._engine = None
         model._resident = set()
 
+    # ------------------------------------------------------------------ stability
+    def _clear_stability(self) -> None:
+        n = len(self.ns_signatures)
+        self.stability_mean_ = np.full(n, np.nan)
+        self.stability_min_ = np.full(n, np.nan)
+        self.cluster_stability_ = [None] * n
+        self.consensus_signatures_ = [None] * n
+        self.assignments_ = [None] * n
+        self.silhouettes_ = [None] * n
+        self.stability_rounds_ = np.zeros(n, dtype=int)
+        self.stability_converged_ = np.zeros(n, dtype=bool)
+
+    def _run_stability(self, batch, slot_of, members, models, n_vars: int) -> None:
+        """One group per entry of ``ns_signatures`` (its members in sweep order), all groups in one launch: in place on the
+        batch when every member of every group lies there, else stand-alone on the models' signatures."""
+        per_k = len(members) // len(self.ns_signatures)
+        groups = [list(range(g * per_k, (g + 1) * per_k)) for g in range(len(self.ns_signatures))]
+        taken = [g for g, k in enumerate(self.ns_signatures) if k <= STABILITY_MAX_SIGNATURES and n_vars <= STABILITY_MAX_FEATURES]
+        if not taken:
+            return
+        errors = [[models[i].reconstruction_error for i in groups[g]] for g in taken]
+        if batch is not None and all(i in slot_of for g in taken for i in groups[g]):
+            results = batch.stability([[slot_of[i] for i in groups[g]] for g in taken], errors, self.stability_max_rounds)
+        else:
+            signatures = [np.stack([np.asarray(models[i].asignatures.X, dtype=np.float64) for i in groups[g]]) for g in taken]
+            results = signature_stability(signatures, errors, self.stability_max_rounds, device=self.device)
+        for g, res in zip(taken, results):
+            self.stability_mean_[g], self.stability_min_[g] = res.stability_mean, res.stability_min
+            self.cluster_stability_[g] = res.cluster_stability
+            self.consensus_signatures_[g] = res.consensus
+            self.assignments_[g] = res.assignments
+            self.silhouettes_[g] = res.silhouette
+            self.stability_rounds_[g], self.stability_converged_[g] = res.n_rounds, res.converged
+
+    def suggest_n_signatures(self, mean_stability: float = 0.8, min_stability: float = 0.2):
+        """The largest K of ``ns_signatures`` whose ``stability_mean_`` is at least ``mean_stability`` and whose
+        ``stability_min_`` is at least ``min_stability`` (the field's customary thresholds), or None if there is none."""
+        if not self.stability:
+            raise ValueError("'suggest_n_signatures' needs a sweep fitted with 'stability=True'.")
+        ok = [k for k, a, b in zip(self.ns_signatures, self.stability_mean_, self.stability_min_) if a >= mean_stability and b >= min_stability]
+        return max(ok) if ok else None
+
     # ------------------------------------------------------------------ fit
     def fit(self, adata, given_parameters: dict[str, Any] | None = None, init_kwargs: dict[str, Any] | None = None,
             fitting_kwargs: dict[str, Any] | None = None, history: bool = True) -> list[KLNMF]:
@@ -145,8 +209,9 @@ class KLNMFSweep:
                 batch = None  # (a device without the batched kernel: every member takes KLNMF.fit)
         slot_of = {i: j for j, i in enumerate(batch_ids)} if batch is not None else {}
         models: list[KLNMF] = []
-        t_init = t_fallback = t_resample = 0.0
+        t_init = t_fallback = t_resample = t_stability = 0.0
         self.resamples_ = None
+        self._clear_stability()
         try:
             if batch is not None:
                 batch.upload_X(np.asarray(adata.X, dtype=np.float64), clip=True)
@@ -194,6 +259,10 @@ class KLNMFSweep:
                         model.history["objective_function"] = objectives[j][1:]
                     model.adata.obs["reconstruction_error"] = kl[j]
             t_batched = time.perf_counter() - tb
+            if self.stability:
+                ta = time.perf_counter()
+                self._run_stability(batch, slot_of, members, models, n_vars)
+                t_stability = time.perf_counter() - ta
         finally:
             if batch is not None:
                 batch.close()
@@ -206,6 +275,8 @@ class KLNMFSweep:
         self.member_steps_ = steps
         self.timings_ = {"total_s": time.perf_counter() - t0, "init_s": t_init, "batched_s": t_batched, "fallback_s": t_fallback,
                          "resample_s": t_resample}
+        if self.stability:
+            self.timings_["stability_s"] = t_stability
         return models
 
     def _next_stop(self, n_iteration: int) -> int:
