@@ -503,6 +503,33 @@ int salnmf_signature_stability(int device, const double* signatures, int n_group
                                int* n_rounds, int* converged, double* consensus, double* a, double* b_dist, double* silhouette,
                                double* cluster_stability, double* stability, double* kernel_ms);
 
+/* ---- Refit of exposures to FIXED signatures, with bootstrap intervals (csrc/salnmf_refit.h).
+ * counts is n_samples x n_features (n_features <= 96), signatures n_signatures x n_features (n_signatures <= 96), used as
+ * they are (never clipped; the caller scales the rows to sum 1).  Every (sample, dataset) pair is a problem of its own,
+ * dataset -1 the counts and dataset r resample r of salnmf_resample_counts(counts, n_resamples, seed), drawn device to
+ * device in chunks whose buffer stays within chunk_bytes (<= 0: 256 MiB; at least one resample per chunk; the results do not
+ * depend on it):
+ *   x = max(row, SALNMF_EPSILON);  h_k = (sum_v x_v) / n_signatures;
+ *   step (update_H, _utils_klnmf.py:258-264): wh = h W, a = x / wh, h_k <- max(h_k sum_v W[k, v] a_v, SALNMF_EPSILON);
+ *   objective: the row's KL divergence as salnmf_samplewise_kl defines it, at iteration 0 and every multiple of
+ *   conv_test_freq; the problem stops at the first test at or after min_iterations with |prev - cur| / |prev| < tol (false
+ *   for a NaN), converged, else at max_iterations.  A problem's result depends on its own row and the signatures only.
+ * Outputs: exposures n_samples x n_signatures; errors (the objective where the problem stopped), n_iterations, converged
+ * n_samples.  With n_resamples R > 0 (R <= 1024: the reduction sorts a signature's R values in one pass):
+ *   n_iterations_resampled, errors_resampled  R x n_samples;  exposures_resampled  NULL, or R x n_samples x n_signatures;
+ *   exposures_mean  n_samples x n_signatures: the sum over r in ascending order, divided by R;
+ *   exposures_quantiles  n_quantiles x n_samples x n_signatures (n_quantiles <= 16): of the R sorted values the one at index
+ *   floor(q (R - 1)) for q <= 0.5 and ceil(q (R - 1)) for q > 0.5.
+ * With R > 0 the counts must be what salnmf_resample_counts accepts.  timings: NULL, or 4 doubles -- milliseconds by device
+ * events of the resample launches, the refit launches and the reduction, and the number of chunks.
+ * Everything is validated on the host before any launch; status 1 and salnmf_last_error otherwise. */
+int salnmf_refit_exposures(int device, const double* counts, int64_t n_samples, int n_features, const double* signatures,
+                           int n_signatures, int n_resamples, uint64_t seed, int n_quantiles, const double* quantiles,
+                           int min_iterations, int max_iterations, int conv_test_freq, double tol, int64_t chunk_bytes,
+                           double* exposures, double* errors, int* n_iterations, int* converged, double* exposures_quantiles,
+                           double* exposures_mean, int* n_iterations_resampled, double* errors_resampled,
+                           double* exposures_resampled, double* timings);
+
 #ifdef __cplusplus
 }
 #endif

@@ -125,6 +125,9 @@ SIGNATURES = {
     # signature stability: salamander_amd/stability.py, batch.py
     "salnmf_batch_stability": (c_int, [_P, c_int, _I, _I, _D, c_int, _I, _I, _I, _D, _D, _D, _D, _D, _D, _D]),
     "salnmf_signature_stability": (c_int, [c_int, _D, c_int, _I, _I, c_int, _D, c_int, _I, _I, _I, _D, _D, _D, _D, _D, _D, _D]),
+    # refit to fixed signatures: salamander_amd/refit.py
+    "salnmf_refit_exposures": (c_int, [c_int, _D, c_int64, c_int, _D, c_int, c_int, c_uint64, c_int, _D, c_int, c_int, c_int, c_double, c_int64,
+                                       _D, _D, _I, _I, _D, _D, _I, _D, _D, _D]),
 }
 
 OBJECTIVE_SLOTS = 256  # SALNMF_OBJECTIVE_SLOTS

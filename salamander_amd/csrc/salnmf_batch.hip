@@ -6,6 +6,7 @@
 #include "../../include/salnmf.h"
 #include "salnmf_batch.h"
 #include "salnmf_error.h"
+#include "salnmf_refit.h"
 #include "salnmf_resample.h"
 #include "salnmf_stability.h"
 
@@ -168,6 +169,14 @@ static int set_list(salnmf_batch* b, int* dev, std::vector<int>& cache, const st
     HIPCK(hipMemcpy(dev, want.data(), want.size() * sizeof(int), hipMemcpyHostToDevice));
     cache = want;
     return 0;
+}
+
+// ---- the resampler as salnmf_refit.hip uses it (salnmf_refit.h): this translation unit holds resample_counts_kernel
+int salnmf::refit_check_counts(const double* X, int64_t N, int V, std::vector<uint32_t>& counts) { return check_counts(X, N, V, counts); }
+
+void salnmf::refit_launch_resample(const uint32_t* counts, double* out, int64_t N, int V, uint64_t seed, int first, int count, hipStream_t stream) {
+    // compact rows, no pad rows, entries max(count, EPSILON): the clip fit() applies to X
+    launch_resample(ResampleArgs{counts, out, N, N, V, V, (uint32_t)seed, (uint32_t)(seed >> 32), SALNMF_EPSILON, (uint32_t)first}, count, stream);
 }
 
 // ---- signature stability (salnmf_stability.h): the two feeders share everything after their own validation

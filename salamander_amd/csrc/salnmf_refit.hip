@@ -1,0 +1,223 @@
+// Host side of the refit to fixed signatures (include/salnmf.h: salnmf_refit_exposures) and its two kernels
+// (salnmf_refit.h: refit_kernel, refit_reduce_kernel).  DESIGN.md section 13.
+#define SALNMF_TEMPLATES_ONLY 1
+#define SALNMF_REFIT_KERNELS 1
+#include "../../include/salnmf.h"
+#include "salnmf_kernels.h"
+#include "salnmf_error.h"
+#include "salnmf_refit.h"
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+using namespace salnmf;
+
+namespace {
+
+// (the destructor waits for the stream first: on an early return no pending copy outlives a buffer, host or device)
+struct RefitBufs {
+    hipStream_t stream = nullptr;
+    std::vector<void*> ptrs;
+    std::vector<hipEvent_t> events;
+    ~RefitBufs() {
+        if (stream) (void)hipStreamSynchronize(stream);
+        for (void* p : ptrs) (void)hipFree(p);
+        for (hipEvent_t e : events) (void)hipEventDestroy(e);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+    template <typename T>
+    T* get(size_t n) {
+        void* p = nullptr;
+        if (hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return nullptr;
+        ptrs.push_back(p);
+        return (T*)p;
+    }
+    // an event recorded on the stream now, or null
+    hipEvent_t mark() {
+        hipEvent_t e = nullptr;
+        if (hipEventCreate(&e) != hipSuccess) return nullptr;
+        events.push_back(e);
+        return hipEventRecord(e, stream) == hipSuccess ? e : nullptr;
+    }
+};
+
+int launch_refit(const RefitArgs& a, int cus, hipStream_t stream) {
+    const int64_t ntiles = (a.P + 15) / 16;
+    // one workgroup per CU (the kernel's registers leave room for one wave per SIMD); waves fetch tiles until the list is empty
+    const dim3 grid((unsigned)std::min<int64_t>((int64_t)cus, (ntiles + WAVES - 1) / WAVES));
+    HIPCK(hipMemsetAsync(a.next_tile, 0, sizeof(unsigned), stream));
+    switch ((a.K + 15) / 16) {
+        case 1: hipLaunchKernelGGL(refit_kernel<1>, grid, dim3(BLOCK), 0, stream, a); break;
+        case 2: hipLaunchKernelGGL(refit_kernel<2>, grid, dim3(BLOCK), 0, stream, a); break;
+        case 3: hipLaunchKernelGGL(refit_kernel<3>, grid, dim3(BLOCK), 0, stream, a); break;
+        case 4: hipLaunchKernelGGL(refit_kernel<4>, grid, dim3(BLOCK), 0, stream, a); break;
+        case 5: hipLaunchKernelGGL(refit_kernel<5>, grid, dim3(BLOCK), 0, stream, a); break;
+        case 6: hipLaunchKernelGGL(refit_kernel<6>, grid, dim3(BLOCK), 0, stream, a); break;
+        default: return fail("no refit kernel for %d signatures", a.K);
+    }
+    HIPCK(hipGetLastError());
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int salnmf_refit_exposures(int device, const double* counts, int64_t n_samples, int n_features, const double* signatures, int n_signatures,
+                                      int n_resamples, uint64_t seed, int n_quantiles, const double* quantiles, int min_iterations, int max_iterations,
+                                      int conv_test_freq, double tol, int64_t chunk_bytes, double* exposures, double* errors, int* n_iterations, int* converged,
+                                      double* exposures_quantiles, double* exposures_mean, int* n_iterations_resampled, double* errors_resampled,
+                                      double* exposures_resampled, double* timings) {
+    const int64_t N = n_samples;
+    const int V = n_features, K = n_signatures, R = n_resamples, Q = n_quantiles;
+    if (!counts || !signatures || !exposures || !errors || !n_iterations || !converged) return fail("null argument");
+    if (N < 1 || N > 0x7fffffff) return fail("n_samples must be in [1, 2^31), got %lld", (long long)N);
+    if (V < 1 || V > VMAX) return fail("n_features must be in [1, %d], got %d", VMAX, V);
+    if (K < 1 || K > REFIT_KMAX) return fail("n_signatures must be in [1, %d], got %d", REFIT_KMAX, K);
+    if (R < 0 || R > REFIT_SORT_MAX) return fail("n_resamples must be in [0, %d], got %d", REFIT_SORT_MAX, R);
+    if (min_iterations < 0 || max_iterations < min_iterations) return fail("need 0 <= min_iterations <= max_iterations, got %d and %d", min_iterations, max_iterations);
+    if (conv_test_freq < 1) return fail("conv_test_freq must be positive, got %d", conv_test_freq);
+    if (!(tol >= 0.0) || !std::isfinite(tol)) return fail("tol must be finite and not negative, got %g", tol);
+    if (Q < 0 || Q > REFIT_MAX_QUANTILES) return fail("n_quantiles must be in [0, %d], got %d", REFIT_MAX_QUANTILES, Q);
+    if (R > 0 && (!exposures_mean || !n_iterations_resampled || !errors_resampled || (Q > 0 && (!quantiles || !exposures_quantiles))))
+        return fail("null output for the resamples");
+    for (int k = 0; k < K; ++k) {
+        double sum = 0.0;
+        for (int v = 0; v < V; ++v) {
+            const double w = signatures[(size_t)k * V + v];
+            if (!std::isfinite(w) || w < 0.0) return fail("signature %d, feature %d: entries must be finite and not negative, got %g", k, v, w);
+            sum += w;
+        }
+        if (!(sum > 0.0) || !std::isfinite(sum)) return fail("signature %d needs a positive finite sum", k);
+    }
+    std::vector<double> x((size_t)N * V);
+    for (size_t i = 0; i < x.size(); ++i) {
+        if (!std::isfinite(counts[i]) || counts[i] < 0.0)
+            return fail("counts must be finite and not negative: row %lld, column %d holds %g", (long long)(i / V), (int)(i % V), counts[i]);
+        x[i] = counts[i] < SALNMF_EPSILON ? SALNMF_EPSILON : counts[i];
+    }
+    RefitReduceArgs red{};
+    std::vector<uint32_t> icounts;
+    if (R > 0) {
+        CK(refit_check_counts(counts, N, V, icounts));
+        for (int i = 0; i < Q; ++i) {
+            const double qv = quantiles[i];
+            if (!(qv >= 0.0 && qv <= 1.0)) return fail("quantile %d must be in [0, 1], got %g", i, qv);
+            // an order statistic, taken outward
+            const double pos = qv * (double)(R - 1);
+            red.index[i] = std::min(R - 1, std::max(0, (int)(qv <= 0.5 ? std::floor(pos) : std::ceil(pos))));
+        }
+    }
+    int ndev = 0;
+    HIPCK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail("device %d out of range (%d visible)", device, ndev);
+    HIPCK(hipSetDevice(device));
+    hipDeviceProp_t prop;
+    HIPCK(hipGetDeviceProperties(&prop, device));
+    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0) return fail("this build targets gfx950 only; device %d is %s", device, prop.gcnArchName);
+    const int cus = prop.multiProcessorCount;
+
+    // resamples per chunk: the [chunk][N][V] buffer stays within chunk_bytes (at least one resample)
+    const int64_t budget = chunk_bytes > 0 ? chunk_bytes : (int64_t)256 << 20;
+    const int chunk = R > 0 ? (int)std::max<int64_t>(1, std::min<int64_t>(R, budget / (int64_t)(sizeof(double) * (size_t)N * V))) : 0;
+
+    // (host buffers of the asynchronous copies live until d's destructor has waited for the stream)
+    RefitBufs d;
+    HIPCK(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
+    const size_t NR = (size_t)N * (size_t)std::max(R, 1);
+    double* dW = d.get<double>((size_t)K * V);
+    double* dX = d.get<double>((size_t)N * V);
+    double* dH = d.get<double>((size_t)N * K);
+    double* derr = d.get<double>((size_t)N);
+    int* dnit = d.get<int>((size_t)N);
+    int* dconv = d.get<int>((size_t)N);
+    unsigned* dnext = d.get<unsigned>(1);
+    if (!dW || !dX || !dH || !derr || !dnit || !dconv || !dnext) return fail("hipMalloc failed (refit of %lld samples)", (long long)N);
+    uint32_t* dcounts = nullptr;
+    double *dXr = nullptr, *dHr = nullptr, *derr_r = nullptr, *dquant = nullptr, *dmean = nullptr;
+    int *dnit_r = nullptr, *dconv_r = nullptr;
+    if (R > 0) {
+        dcounts = d.get<uint32_t>(icounts.size());
+        dXr = d.get<double>((size_t)chunk * N * V);
+        dHr = d.get<double>(NR * K);
+        derr_r = d.get<double>(NR);
+        dnit_r = d.get<int>(NR);
+        dconv_r = d.get<int>(NR);
+        dquant = d.get<double>((size_t)std::max(Q, 1) * N * K);
+        dmean = d.get<double>((size_t)N * K);
+        if (!dcounts || !dXr || !dHr || !derr_r || !dnit_r || !dconv_r || !dquant || !dmean)
+            return fail("hipMalloc failed (%d resamples of %lld x %d, %d signatures)", R, (long long)N, V, K);
+        HIPCK(hipMemcpyAsync(dcounts, icounts.data(), icounts.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+    }
+    HIPCK(hipMemcpyAsync(dW, signatures, (size_t)K * V * sizeof(double), hipMemcpyHostToDevice, d.stream));
+    HIPCK(hipMemcpyAsync(dX, x.data(), x.size() * sizeof(double), hipMemcpyHostToDevice, d.stream));
+
+    RefitArgs a{dX, dW, dH, derr, dnit, dconv, dnext, N, V, K, min_iterations, max_iterations, conv_test_freq, tol};
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> t_refit, t_resample, t_reduce;
+    auto timed = [&](std::vector<std::pair<hipEvent_t, hipEvent_t>>& into, auto&& body) -> int {
+        hipEvent_t e0 = timings ? d.mark() : nullptr;
+        CK(body());
+        hipEvent_t e1 = timings ? d.mark() : nullptr;
+        if (timings && (!e0 || !e1)) return fail("event record failed");
+        if (timings) into.emplace_back(e0, e1);
+        return 0;
+    };
+    CK(timed(t_refit, [&] { return launch_refit(a, cus, d.stream); }));
+    int n_chunks = 0;
+    for (int first = 0; first < R; first += chunk, ++n_chunks) {
+        const int count = std::min(chunk, R - first);
+        CK(timed(t_resample, [&]() -> int {
+            refit_launch_resample(dcounts, dXr, N, V, seed, first, count, d.stream);
+            HIPCK(hipGetLastError());
+            return 0;
+        }));
+        RefitArgs c = a;
+        c.X = dXr;
+        c.P = (int64_t)count * N;
+        c.H = dHr + (size_t)first * N * K;
+        c.err = derr_r + (size_t)first * N;
+        c.nit = dnit_r + (size_t)first * N;
+        c.conv = dconv_r + (size_t)first * N;
+        CK(timed(t_refit, [&] { return launch_refit(c, cus, d.stream); }));
+    }
+    if (R > 0) {
+        red.H = dHr;
+        red.quant = dquant;
+        red.mean = dmean;
+        red.N = N;
+        red.K = K;
+        red.R = R;
+        red.Q = Q;
+        red.R2 = 1;
+        while (red.R2 < R) red.R2 <<= 1;
+        CK(timed(t_reduce, [&]() -> int {
+            hipLaunchKernelGGL(refit_reduce_kernel, dim3((unsigned)N), dim3(REFIT_SORT_BLOCK), 0, d.stream, red);
+            HIPCK(hipGetLastError());
+            return 0;
+        }));
+        if (Q > 0) HIPCK(hipMemcpyAsync(exposures_quantiles, dquant, (size_t)Q * N * K * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+        HIPCK(hipMemcpyAsync(exposures_mean, dmean, (size_t)N * K * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+        HIPCK(hipMemcpyAsync(n_iterations_resampled, dnit_r, NR * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+        HIPCK(hipMemcpyAsync(errors_resampled, derr_r, NR * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+        if (exposures_resampled) HIPCK(hipMemcpyAsync(exposures_resampled, dHr, NR * K * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    }
+    HIPCK(hipMemcpyAsync(exposures, dH, (size_t)N * K * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(errors, derr, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(n_iterations, dnit, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(converged, dconv, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipStreamSynchronize(d.stream));
+    if (timings) {
+        const std::vector<std::pair<hipEvent_t, hipEvent_t>>* sets[3] = {&t_resample, &t_refit, &t_reduce};
+        for (int i = 0; i < 3; ++i) {
+            double total = 0.0;
+            for (const auto& pr : *sets[i]) {
+                float ms = 0.f;
+                HIPCK(hipEventElapsedTime(&ms, pr.first, pr.second));
+                total += (double)ms;
+            }
+            timings[i] = total;
+        }
+        timings[3] = (double)n_chunks;
+    }
+    return 0;
+}

@@ -26,6 +26,7 @@ struct ResampleArgs {
     int V, ld;                            // ld >= V: columns beyond V are written as zeros
     uint32_t key0, key1;
     double floor;                         // entries of the N x V block are max(count, floor): 0 (raw) or SALNMF_EPSILON
+    uint32_t first;                       // slot 0 of `out` holds resample `first` (a chunk of a longer series: salnmf_refit.h)
 };
 
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&o)[4]) {
@@ -65,8 +66,8 @@ __global__ void __launch_bounds__(RESAMPLE_BLOCK) resample_counts_kernel(Resampl
     __shared__ uint32_t part[RESAMPLE_BLOCK];
     const int tid = threadIdx.x;
     const int64_t n = blockIdx.x;
-    const uint32_t r = blockIdx.y;
-    double* out = a.out + ((size_t)r * a.rows_out + n) * a.ld;
+    const uint32_t r = blockIdx.y + a.first;
+    double* out = a.out + ((size_t)blockIdx.y * a.rows_out + n) * a.ld;
     if (n >= a.N) {  // a pad row of the batch layout
         for (int v = tid; v < a.ld; v += RESAMPLE_BLOCK) out[v] = 0.0;
         return;
