@@ -530,6 +530,36 @@ int salnmf_refit_exposures(int device, const double* counts, int64_t n_samples, 
                            double* exposures_mean, int* n_iterations_resampled, double* errors_resampled,
                            double* exposures_resampled, double* timings);
 
+/* ---- Sparse assignment: which of the fixed signatures are active in each sample (csrc/salnmf_assign.h, DESIGN.md
+ * section 14).  Arguments, problems, resamples and chunking as salnmf_refit_exposures, plus max_kl_increase (finite) and the
+ * requirement max_iterations % conv_test_freq == 0 (the solves of a problem follow one another inside one wave, whose tests
+ * stay on common iterations).  Contract, per problem:
+ *   a SOLVE from a start h with an active set A is the refit's iteration on the active entries -- the same step, objective and
+ *   stop rule, iterations counted from 0 at the start of the solve, the objective evaluated at iteration 0 and at every
+ *   multiple of conv_test_freq; inactive entries are exactly 0.0 and stay 0.0 (never clipped up to SALNMF_EPSILON);
+ *   phase 0: A = all signatures, h_k = (sum_v x_v) / n_signatures, solve: bit for bit salnmf_refit_exposures' exposures, error,
+ *   iteration count and convergence flag (the dense_* outputs);
+ *   rounds: the candidate c is the active, not yet protected signature of smallest h, lowest index on equal values; the
+ *   procedure stops when there is none or one signature is left.  Trial: copy h, set entry c to 0.0, solve with A \ {c}:
+ *   h', f'.  If f' - f <= max_kl_increase (false for a NaN) A, h, f become the trial's; otherwise c is protected for the rest
+ *   of the procedure and h, f stay.  Every signature is tried at most once.
+ * Outputs: exposures n_samples x n_signatures (0.0 off the support); active (1 / 0), removal_round (the 0-based number of the
+ * trial that removed k, -1 if kept), kl_increase (f' - f of the trial that tested k, NaN if never tested) n_samples x
+ * n_signatures; errors (f), n_trials, n_iterations (summed over the solves), converged (every solve stopped on its
+ * tolerance) n_samples.  With n_resamples R > 0 the whole procedure runs for every resample, and the R exposures are reduced
+ * on the device: selection_frequency n_samples x n_signatures = (resamples with exposure > 0) / R, counted in integers;
+ * exposures_mean and exposures_quantiles by salnmf_refit_exposures' rules, zeros included; exposures_resampled NULL, or R x
+ * n_samples x n_signatures.  timings: NULL, or 4 doubles -- milliseconds by device events of the resample launches, the
+ * assignment launches and the reductions, and the number of chunks.
+ * Everything is validated on the host before any launch; status 1 and salnmf_last_error otherwise. */
+int salnmf_assign_signatures(int device, const double* counts, int64_t n_samples, int n_features, const double* signatures,
+                             int n_signatures, int n_resamples, uint64_t seed, int n_quantiles, const double* quantiles,
+                             int min_iterations, int max_iterations, int conv_test_freq, double tol, double max_kl_increase,
+                             int64_t chunk_bytes, double* exposures, int* active, double* errors, int* removal_round,
+                             double* kl_increase, int* n_trials, int64_t* n_iterations, int* converged, double* dense_exposures,
+                             double* dense_errors, int* dense_n_iterations, int* dense_converged, double* selection_frequency,
+                             double* exposures_quantiles, double* exposures_mean, double* exposures_resampled, double* timings);
+
 #ifdef __cplusplus
 }
 #endif

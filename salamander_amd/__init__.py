@@ -9,10 +9,12 @@ extension or a gfx950 device is missing -- there is no CPU fallback.
 from . import models
 from ._lib import EngineUnavailable
 from .anndata_compat import AnnData, MuData
+from .assign import AssignResult, assign_signatures
 from .engine import Engine
 from .refit import RefitResult, refit_exposures
 from .resample import resample_counts
 from .stability import signature_stability
 
 __version__ = "0.1.0"
-__all__ = ["models", "Engine", "AnnData", "MuData", "EngineUnavailable", "resample_counts", "signature_stability", "refit_exposures", "RefitResult"]
+__all__ = ["models", "Engine", "AnnData", "MuData", "EngineUnavailable", "resample_counts", "signature_stability", "refit_exposures", "RefitResult", "assign_signatures",
+           "AssignResult"]

@@ -128,6 +128,9 @@ SIGNATURES = {
     # refit to fixed signatures: salamander_amd/refit.py
     "salnmf_refit_exposures": (c_int, [c_int, _D, c_int64, c_int, _D, c_int, c_int, c_uint64, c_int, _D, c_int, c_int, c_int, c_double, c_int64,
                                        _D, _D, _I, _I, _D, _D, _I, _D, _D, _D]),
+    # sparse assignment to fixed signatures: salamander_amd/assign.py
+    "salnmf_assign_signatures": (c_int, [c_int, _D, c_int64, c_int, _D, c_int, c_int, c_uint64, c_int, _D, c_int, c_int, c_int, c_double, c_double, c_int64,
+                                         _D, _I, _D, _I, _D, _I, POINTER(c_int64), _I, _D, _D, _I, _I, _D, _D, _D, _D, _D]),
 }
 
 OBJECTIVE_SLOTS = 256  # SALNMF_OBJECTIVE_SLOTS

@@ -1,11 +1,13 @@
 // Host side of the refit to fixed signatures (include/salnmf.h: salnmf_refit_exposures) and its two kernels
-// (salnmf_refit.h: refit_kernel, refit_reduce_kernel).  DESIGN.md section 13.
+// (salnmf_refit.h: refit_kernel, refit_reduce_kernel); and of the sparse assignment built on it
+// (salnmf_assign_signatures; salnmf_assign.h: assign_kernel, assign_selection_kernel), DESIGN.md section 14.
 #define SALNMF_TEMPLATES_ONLY 1
 #define SALNMF_REFIT_KERNELS 1
 #include "../../include/salnmf.h"
 #include "salnmf_kernels.h"
 #include "salnmf_error.h"
 #include "salnmf_refit.h"
+#include "salnmf_assign.h"
 
 #include <algorithm>
 #include <cmath>
@@ -43,6 +45,63 @@ struct RefitBufs {
     }
 };
 
+// What both entry points check and prepare before any launch: the ranges, the signatures, the counts clipped to EPSILON
+// (and as integers for the resampler when R > 0), the quantiles' indices, the device and its CU count.
+struct RefitInputs {
+    std::vector<double> x;
+    std::vector<uint32_t> icounts;
+    RefitReduceArgs red{};
+    int cus = 0;
+};
+
+int refit_prepare(int device, const double* counts, int64_t N, int V, const double* signatures, int K, int R, int Q, const double* quantiles,
+                  int min_iterations, int max_iterations, int conv_test_freq, double tol, bool resample_outputs, RefitInputs& in) {
+    if (N < 1 || N > 0x7fffffff) return fail("n_samples must be in [1, 2^31), got %lld", (long long)N);
+    if (V < 1 || V > VMAX) return fail("n_features must be in [1, %d], got %d", VMAX, V);
+    if (K < 1 || K > REFIT_KMAX) return fail("n_signatures must be in [1, %d], got %d", REFIT_KMAX, K);
+    if (R < 0 || R > REFIT_SORT_MAX) return fail("n_resamples must be in [0, %d], got %d", REFIT_SORT_MAX, R);
+    if (min_iterations < 0 || max_iterations < min_iterations) return fail("need 0 <= min_iterations <= max_iterations, got %d and %d", min_iterations, max_iterations);
+    if (conv_test_freq < 1) return fail("conv_test_freq must be positive, got %d", conv_test_freq);
+    if (!(tol >= 0.0) || !std::isfinite(tol)) return fail("tol must be finite and not negative, got %g", tol);
+    if (Q < 0 || Q > REFIT_MAX_QUANTILES) return fail("n_quantiles must be in [0, %d], got %d", REFIT_MAX_QUANTILES, Q);
+    if (R > 0 && !resample_outputs) return fail("null output for the resamples");
+    for (int k = 0; k < K; ++k) {
+        double sum = 0.0;
+        for (int v = 0; v < V; ++v) {
+            const double w = signatures[(size_t)k * V + v];
+            if (!std::isfinite(w) || w < 0.0) return fail("signature %d, feature %d: entries must be finite and not negative, got %g", k, v, w);
+            sum += w;
+        }
+        if (!(sum > 0.0) || !std::isfinite(sum)) return fail("signature %d needs a positive finite sum", k);
+    }
+    std::vector<double>& x = in.x;
+    x.resize((size_t)N * V);
+    for (size_t i = 0; i < x.size(); ++i) {
+        if (!std::isfinite(counts[i]) || counts[i] < 0.0)
+            return fail("counts must be finite and not negative: row %lld, column %d holds %g", (long long)(i / V), (int)(i % V), counts[i]);
+        x[i] = counts[i] < SALNMF_EPSILON ? SALNMF_EPSILON : counts[i];
+    }
+    if (R > 0) {
+        CK(refit_check_counts(counts, N, V, in.icounts));
+        for (int i = 0; i < Q; ++i) {
+            const double qv = quantiles[i];
+            if (!(qv >= 0.0 && qv <= 1.0)) return fail("quantile %d must be in [0, 1], got %g", i, qv);
+            // an order statistic, taken outward
+            const double pos = qv * (double)(R - 1);
+            in.red.index[i] = std::min(R - 1, std::max(0, (int)(qv <= 0.5 ? std::floor(pos) : std::ceil(pos))));
+        }
+    }
+    int ndev = 0;
+    HIPCK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail("device %d out of range (%d visible)", device, ndev);
+    HIPCK(hipSetDevice(device));
+    hipDeviceProp_t prop;
+    HIPCK(hipGetDeviceProperties(&prop, device));
+    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0) return fail("this build targets gfx950 only; device %d is %s", device, prop.gcnArchName);
+    in.cus = prop.multiProcessorCount;
+    return 0;
+}
+
 int launch_refit(const RefitArgs& a, int cus, hipStream_t stream) {
     const int64_t ntiles = (a.P + 15) / 16;
     // one workgroup per CU (the kernel's registers leave room for one wave per SIMD); waves fetch tiles until the list is empty
@@ -61,6 +120,23 @@ int launch_refit(const RefitArgs& a, int cus, hipStream_t stream) {
     return 0;
 }
 
+int launch_assign(const AssignArgs& a, int cus, hipStream_t stream) {
+    const int64_t ntiles = (a.P + 15) / 16;
+    const dim3 grid((unsigned)std::min<int64_t>((int64_t)cus, (ntiles + WAVES - 1) / WAVES));  // as launch_refit
+    HIPCK(hipMemsetAsync(a.next_tile, 0, sizeof(unsigned), stream));
+    switch ((a.K + 15) / 16) {
+        case 1: hipLaunchKernelGGL(assign_kernel<1>, grid, dim3(BLOCK), 0, stream, a); break;
+        case 2: hipLaunchKernelGGL(assign_kernel<2>, grid, dim3(BLOCK), 0, stream, a); break;
+        case 3: hipLaunchKernelGGL(assign_kernel<3>, grid, dim3(BLOCK), 0, stream, a); break;
+        case 4: hipLaunchKernelGGL(assign_kernel<4>, grid, dim3(BLOCK), 0, stream, a); break;
+        case 5: hipLaunchKernelGGL(assign_kernel<5>, grid, dim3(BLOCK), 0, stream, a); break;
+        case 6: hipLaunchKernelGGL(assign_kernel<6>, grid, dim3(BLOCK), 0, stream, a); break;
+        default: return fail("no assignment kernel for %d signatures", a.K);
+    }
+    HIPCK(hipGetLastError());
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int salnmf_refit_exposures(int device, const double* counts, int64_t n_samples, int n_features, const double* signatures, int n_signatures,
@@ -71,51 +147,13 @@ extern "C" int salnmf_refit_exposures(int device, const double* counts, int64_t 
     const int64_t N = n_samples;
     const int V = n_features, K = n_signatures, R = n_resamples, Q = n_quantiles;
     if (!counts || !signatures || !exposures || !errors || !n_iterations || !converged) return fail("null argument");
-    if (N < 1 || N > 0x7fffffff) return fail("n_samples must be in [1, 2^31), got %lld", (long long)N);
-    if (V < 1 || V > VMAX) return fail("n_features must be in [1, %d], got %d", VMAX, V);
-    if (K < 1 || K > REFIT_KMAX) return fail("n_signatures must be in [1, %d], got %d", REFIT_KMAX, K);
-    if (R < 0 || R > REFIT_SORT_MAX) return fail("n_resamples must be in [0, %d], got %d", REFIT_SORT_MAX, R);
-    if (min_iterations < 0 || max_iterations < min_iterations) return fail("need 0 <= min_iterations <= max_iterations, got %d and %d", min_iterations, max_iterations);
-    if (conv_test_freq < 1) return fail("conv_test_freq must be positive, got %d", conv_test_freq);
-    if (!(tol >= 0.0) || !std::isfinite(tol)) return fail("tol must be finite and not negative, got %g", tol);
-    if (Q < 0 || Q > REFIT_MAX_QUANTILES) return fail("n_quantiles must be in [0, %d], got %d", REFIT_MAX_QUANTILES, Q);
-    if (R > 0 && (!exposures_mean || !n_iterations_resampled || !errors_resampled || (Q > 0 && (!quantiles || !exposures_quantiles))))
-        return fail("null output for the resamples");
-    for (int k = 0; k < K; ++k) {
-        double sum = 0.0;
-        for (int v = 0; v < V; ++v) {
-            const double w = signatures[(size_t)k * V + v];
-            if (!std::isfinite(w) || w < 0.0) return fail("signature %d, feature %d: entries must be finite and not negative, got %g", k, v, w);
-            sum += w;
-        }
-        if (!(sum > 0.0) || !std::isfinite(sum)) return fail("signature %d needs a positive finite sum", k);
-    }
-    std::vector<double> x((size_t)N * V);
-    for (size_t i = 0; i < x.size(); ++i) {
-        if (!std::isfinite(counts[i]) || counts[i] < 0.0)
-            return fail("counts must be finite and not negative: row %lld, column %d holds %g", (long long)(i / V), (int)(i % V), counts[i]);
-        x[i] = counts[i] < SALNMF_EPSILON ? SALNMF_EPSILON : counts[i];
-    }
-    RefitReduceArgs red{};
-    std::vector<uint32_t> icounts;
-    if (R > 0) {
-        CK(refit_check_counts(counts, N, V, icounts));
-        for (int i = 0; i < Q; ++i) {
-            const double qv = quantiles[i];
-            if (!(qv >= 0.0 && qv <= 1.0)) return fail("quantile %d must be in [0, 1], got %g", i, qv);
-            // an order statistic, taken outward
-            const double pos = qv * (double)(R - 1);
-            red.index[i] = std::min(R - 1, std::max(0, (int)(qv <= 0.5 ? std::floor(pos) : std::ceil(pos))));
-        }
-    }
-    int ndev = 0;
-    HIPCK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail("device %d out of range (%d visible)", device, ndev);
-    HIPCK(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    HIPCK(hipGetDeviceProperties(&prop, device));
-    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0) return fail("this build targets gfx950 only; device %d is %s", device, prop.gcnArchName);
-    const int cus = prop.multiProcessorCount;
+    RefitInputs in;
+    CK(refit_prepare(device, counts, N, V, signatures, K, R, Q, quantiles, min_iterations, max_iterations, conv_test_freq, tol,
+                     exposures_mean && n_iterations_resampled && errors_resampled && (Q <= 0 || (quantiles && exposures_quantiles)), in));
+    const std::vector<double>& x = in.x;
+    const std::vector<uint32_t>& icounts = in.icounts;
+    RefitReduceArgs& red = in.red;
+    const int cus = in.cus;
 
     // resamples per chunk: the [chunk][N][V] buffer stays within chunk_bytes (at least one resample)
     const int64_t budget = chunk_bytes > 0 ? chunk_bytes : (int64_t)256 << 20;
@@ -211,6 +249,156 @@ extern "C" int salnmf_refit_exposures(int device, const double* counts, int64_t 
         for (int i = 0; i < 3; ++i) {
             double total = 0.0;
             for (const auto& pr : *sets[i]) {
+                float ms = 0.f;
+                HIPCK(hipEventElapsedTime(&ms, pr.first, pr.second));
+                total += (double)ms;
+            }
+            timings[i] = total;
+        }
+        timings[3] = (double)n_chunks;
+    }
+    return 0;
+}
+
+extern "C" int salnmf_assign_signatures(int device, const double* counts, int64_t n_samples, int n_features, const double* signatures, int n_signatures,
+                                        int n_resamples, uint64_t seed, int n_quantiles, const double* quantiles, int min_iterations, int max_iterations,
+                                        int conv_test_freq, double tol, double max_kl_increase, int64_t chunk_bytes, double* exposures, int* active,
+                                        double* errors, int* removal_round, double* kl_increase, int* n_trials, int64_t* n_iterations, int* converged,
+                                        double* dense_exposures, double* dense_errors, int* dense_n_iterations, int* dense_converged,
+                                        double* selection_frequency, double* exposures_quantiles, double* exposures_mean, double* exposures_resampled,
+                                        double* timings) {
+    const int64_t N = n_samples;
+    const int V = n_features, K = n_signatures, R = n_resamples, Q = n_quantiles;
+    if (!counts || !signatures || !exposures || !active || !errors || !removal_round || !kl_increase || !n_trials || !n_iterations || !converged ||
+        !dense_exposures || !dense_errors || !dense_n_iterations || !dense_converged)
+        return fail("null argument");
+    if (!std::isfinite(max_kl_increase)) return fail("max_kl_increase must be finite, got %g", max_kl_increase);
+    // (solves follow one another inside one wave, and the tests of its 16 problems must fall on the same iterations)
+    if (conv_test_freq >= 1 && max_iterations >= 0 && max_iterations % conv_test_freq != 0)
+        return fail("max_iterations must be a multiple of conv_test_freq, got %d and %d", max_iterations, conv_test_freq);
+    RefitInputs in;
+    CK(refit_prepare(device, counts, N, V, signatures, K, R, Q, quantiles, min_iterations, max_iterations, conv_test_freq, tol,
+                     selection_frequency && exposures_mean && (Q <= 0 || (quantiles && exposures_quantiles)), in));
+    const int cus = in.cus;
+    const int64_t budget = chunk_bytes > 0 ? chunk_bytes : (int64_t)256 << 20;
+    const int chunk = R > 0 ? (int)std::max<int64_t>(1, std::min<int64_t>(R, budget / (int64_t)(sizeof(double) * (size_t)N * V))) : 0;
+
+    RefitBufs d;
+    HIPCK(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
+    const size_t NK = (size_t)N * K, NR = (size_t)N * (size_t)std::max(R, 1);
+    double* dW = d.get<double>((size_t)K * V);
+    double* dX = d.get<double>((size_t)N * V);
+    double* dH = d.get<double>(NK);
+    double* dHd = d.get<double>(NK);
+    double* dkl = d.get<double>(NK);
+    int* dact = d.get<int>(NK);
+    int* dround = d.get<int>(NK);
+    double* derr = d.get<double>((size_t)N);
+    double* derr_d = d.get<double>((size_t)N);
+    long long* dnit = d.get<long long>((size_t)N);
+    int* dconv = d.get<int>((size_t)N);
+    int* dntr = d.get<int>((size_t)N);
+    int* dnit_d = d.get<int>((size_t)N);
+    int* dconv_d = d.get<int>((size_t)N);
+    unsigned* dnext = d.get<unsigned>(1);
+    if (!dW || !dX || !dH || !dHd || !dkl || !dact || !dround || !derr || !derr_d || !dnit || !dconv || !dntr || !dnit_d || !dconv_d || !dnext)
+        return fail("hipMalloc failed (assignment of %lld samples)", (long long)N);
+    uint32_t* dcounts = nullptr;
+    double *dXr = nullptr, *dHr = nullptr, *derr_r = nullptr, *dquant = nullptr, *dmean = nullptr, *dfreq = nullptr;
+    long long* dnit_r = nullptr;
+    int *dconv_r = nullptr, *dntr_r = nullptr;
+    if (R > 0) {
+        dcounts = d.get<uint32_t>(in.icounts.size());
+        dXr = d.get<double>((size_t)chunk * N * V);
+        dHr = d.get<double>(NR * K);
+        derr_r = d.get<double>(NR);
+        dnit_r = d.get<long long>(NR);
+        dconv_r = d.get<int>(NR);
+        dntr_r = d.get<int>(NR);
+        dquant = d.get<double>((size_t)std::max(Q, 1) * NK);
+        dmean = d.get<double>(NK);
+        dfreq = d.get<double>(NK);
+        if (!dcounts || !dXr || !dHr || !derr_r || !dnit_r || !dconv_r || !dntr_r || !dquant || !dmean || !dfreq)
+            return fail("hipMalloc failed (%d resamples of %lld x %d, %d signatures)", R, (long long)N, V, K);
+        HIPCK(hipMemcpyAsync(dcounts, in.icounts.data(), in.icounts.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+    }
+    HIPCK(hipMemcpyAsync(dW, signatures, (size_t)K * V * sizeof(double), hipMemcpyHostToDevice, d.stream));
+    HIPCK(hipMemcpyAsync(dX, in.x.data(), in.x.size() * sizeof(double), hipMemcpyHostToDevice, d.stream));
+
+    AssignArgs a{dX, dW, dH, derr, dnit, dconv, dntr, dact, dround, dkl, dHd, derr_d, dnit_d, dconv_d, dnext, N, V, K,
+                 min_iterations, max_iterations, conv_test_freq, tol, max_kl_increase};
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> spans[3];  // resample, assign, reduce
+    auto timed = [&](int which, auto&& body) -> int {
+        hipEvent_t e0 = timings ? d.mark() : nullptr;
+        CK(body());
+        hipEvent_t e1 = timings ? d.mark() : nullptr;
+        if (timings && (!e0 || !e1)) return fail("event record failed");
+        if (timings) spans[which].emplace_back(e0, e1);
+        return 0;
+    };
+    CK(timed(1, [&] { return launch_assign(a, cus, d.stream); }));
+    int n_chunks = 0;
+    for (int first = 0; first < R; first += chunk, ++n_chunks) {
+        const int count = std::min(chunk, R - first);
+        CK(timed(0, [&]() -> int {
+            refit_launch_resample(dcounts, dXr, N, V, seed, first, count, d.stream);
+            HIPCK(hipGetLastError());
+            return 0;
+        }));
+        // a resample's problems keep their exposures only: no per-signature record, no phase-0 copy
+        AssignArgs c = a;
+        c.X = dXr;
+        c.P = (int64_t)count * N;
+        c.H = dHr + (size_t)first * NK;
+        c.err = derr_r + (size_t)first * N;
+        c.nit = dnit_r + (size_t)first * N;
+        c.conv = dconv_r + (size_t)first * N;
+        c.ntrials = dntr_r + (size_t)first * N;
+        c.active = nullptr, c.round = nullptr, c.kl = nullptr;
+        c.dH = nullptr, c.derr = nullptr, c.dnit = nullptr, c.dconv = nullptr;
+        CK(timed(1, [&] { return launch_assign(c, cus, d.stream); }));
+    }
+    if (R > 0) {
+        RefitReduceArgs& red = in.red;
+        red.H = dHr;
+        red.quant = dquant;
+        red.mean = dmean;
+        red.N = N;
+        red.K = K;
+        red.R = R;
+        red.Q = Q;
+        red.R2 = 1;
+        while (red.R2 < R) red.R2 <<= 1;
+        const AssignSelectArgs sel{dHr, dfreq, (int64_t)NK, R};
+        CK(timed(2, [&]() -> int {
+            hipLaunchKernelGGL(refit_reduce_kernel, dim3((unsigned)N), dim3(REFIT_SORT_BLOCK), 0, d.stream, red);
+            HIPCK(hipGetLastError());
+            hipLaunchKernelGGL(assign_selection_kernel, dim3((unsigned)((NK + 255) / 256)), dim3(256), 0, d.stream, sel);
+            HIPCK(hipGetLastError());
+            return 0;
+        }));
+        if (Q > 0) HIPCK(hipMemcpyAsync(exposures_quantiles, dquant, (size_t)Q * NK * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+        HIPCK(hipMemcpyAsync(exposures_mean, dmean, NK * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+        HIPCK(hipMemcpyAsync(selection_frequency, dfreq, NK * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+        if (exposures_resampled) HIPCK(hipMemcpyAsync(exposures_resampled, dHr, NR * K * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    }
+    HIPCK(hipMemcpyAsync(exposures, dH, NK * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(active, dact, NK * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(removal_round, dround, NK * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(kl_increase, dkl, NK * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(errors, derr, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(n_trials, dntr, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(n_iterations, dnit, (size_t)N * sizeof(int64_t), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(converged, dconv, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(dense_exposures, dHd, NK * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(dense_errors, derr_d, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(dense_n_iterations, dnit_d, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(dense_converged, dconv_d, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipStreamSynchronize(d.stream));
+    if (timings) {
+        for (int i = 0; i < 3; ++i) {
+            double total = 0.0;
+            for (const auto& pr : spans[i]) {
                 float ms = 0.f;
                 HIPCK(hipEventElapsedTime(&ms, pr.first, pr.second));
                 total += (double)ms;

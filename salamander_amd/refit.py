@@ -77,17 +77,9 @@ def normalize_signatures(signatures) -> np.ndarray:
     return np.ascontiguousarray(S / sums)
 
 
-def refit_exposures(counts, signatures, n_resamples: int = 0, resample_seed: int = 0, quantiles=(0.025, 0.5, 0.975),
-                    min_iterations: int = 500, max_iterations: int = 10000, conv_test_freq: int = 10, tol: float = 1e-7,
-                    keep_resamples: bool = False, device: int = 0, chunk_bytes: int | None = None) -> RefitResult:
-    """Exposures of every row of ``counts (N, V)`` to the fixed ``signatures (K, V)``, K <= 96 and V <= 96.
-
-    The signature rows are divided by their sums and used as they are (never clipped).  Every sample is iterated and
-    stopped on its own (module docstring); ``n_resamples`` adds the bootstrap: ``exposures_mean``, ``exposures_quantiles``
-    (existing values: index ``floor(q (R - 1))`` of the sorted resamples for q <= 0.5, ``ceil`` above) and, with
-    ``keep_resamples``, every resample's exposures.  ``chunk_bytes`` bounds the device buffer the resamples are drawn into
-    (default 256 MiB; the result does not depend on it).  Anything out of range is a ``ValueError`` before the device is touched."""
-    t_start = time.perf_counter()
+def check_arguments(counts, signatures, n_resamples, resample_seed, quantiles, min_iterations, max_iterations, conv_test_freq, tol, chunk_bytes):
+    """Everything :func:`refit_exposures` (and ``assign_signatures``) refuses before it touches a device, as ``ValueError``:
+    returns ``(X, S, R, seed, min_it, max_it, freq, tol, q, chunk)`` ready for the C call."""
     if isinstance(counts, _ANNDATA) and isinstance(signatures, _ANNDATA):
         check_given_asignatures(signatures, counts, signatures.n_obs)
     X = np.ascontiguousarray(np.asarray(counts.X if isinstance(counts, _ANNDATA) else counts), dtype=np.float64)
@@ -117,6 +109,23 @@ def refit_exposures(counts, signatures, n_resamples: int = 0, resample_seed: int
     chunk = DEFAULT_CHUNK_BYTES if chunk_bytes is None else _check_int("chunk_bytes", chunk_bytes, 1)
     if R > 0:
         check_counts(X)
+    return X, S, R, seed, min_it, max_it, freq, tol, q, chunk
+
+
+def refit_exposures(counts, signatures, n_resamples: int = 0, resample_seed: int = 0, quantiles=(0.025, 0.5, 0.975),
+                    min_iterations: int = 500, max_iterations: int = 10000, conv_test_freq: int = 10, tol: float = 1e-7,
+                    keep_resamples: bool = False, device: int = 0, chunk_bytes: int | None = None) -> RefitResult:
+    """Exposures of every row of ``counts (N, V)`` to the fixed ``signatures (K, V)``, K <= 96 and V <= 96.
+
+    The signature rows are divided by their sums and used as they are (never clipped).  Every sample is iterated and
+    stopped on its own (module docstring); ``n_resamples`` adds the bootstrap: ``exposures_mean``, ``exposures_quantiles``
+    (existing values: index ``floor(q (R - 1))`` of the sorted resamples for q <= 0.5, ``ceil`` above) and, with
+    ``keep_resamples``, every resample's exposures.  ``chunk_bytes`` bounds the device buffer the resamples are drawn into
+    (default 256 MiB; the result does not depend on it).  Anything out of range is a ``ValueError`` before the device is touched."""
+    t_start = time.perf_counter()
+    X, S, R, seed, min_it, max_it, freq, tol, q, chunk = check_arguments(counts, signatures, n_resamples, resample_seed, quantiles, min_iterations,
+                                                                         max_iterations, conv_test_freq, tol, chunk_bytes)
+    (N, V), K = X.shape, S.shape[0]
     lib = _lib.load()
     if lib.salnmf_device_count() < 1:
         raise _lib.EngineUnavailable("no HIP device visible: salamander_amd runs on MI355X (gfx950) only and has no CPU fallback.")
