@@ -202,6 +202,24 @@ def load():
     return lib
 
 
+def load_with_device():
+    """:func:`load`, and ``EngineUnavailable`` where the library sees no device."""
+    lib = load()
+    if lib.salnmf_device_count() < 1:
+        raise EngineUnavailable("no HIP device visible: salamander_amd runs on MI355X (gfx950) only and has no CPU fallback.")
+    return lib
+
+
+def pointer(a):
+    """The argument a float64, int32 or int64 array is passed as; null for ``None`` and for an empty array."""
+    if a is None or a.size == 0:
+        return None
+    types = {"float64": _D, "int32": _I, "int64": POINTER(c_int64)}
+    if a.dtype.name not in types:
+        raise TypeError(f"no pointer type for an array of {a.dtype.name}")
+    return a.ctypes.data_as(types[a.dtype.name])
+
+
 def mapped_runtime_libraries() -> dict:
     """Paths of the HIP runtime and RCCL copies mapped into this process: ``{"libamdhip64": [...], "librccl": [...]}``."""
     import re

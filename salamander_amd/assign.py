@@ -20,7 +20,6 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from .engine import _ptr
 from .refit import check_arguments
 
 
@@ -65,9 +64,7 @@ def assign_signatures(counts, signatures, max_kl_increase: float = 1.92, n_resam
         raise ValueError("'max_kl_increase' must be a finite number.")
     thr = float(max_kl_increase)
     (N, V), K = X.shape, S.shape[0]
-    lib = _lib.load()
-    if lib.salnmf_device_count() < 1:
-        raise _lib.EngineUnavailable("no HIP device visible: salamander_amd runs on MI355X (gfx950) only and has no CPU fallback.")
+    lib = _lib.load_with_device()
 
     Q = int(q.size)
     f64 = lambda *shape: np.empty(shape, dtype=np.float64)  # noqa: E731
@@ -80,12 +77,11 @@ def assign_signatures(counts, signatures, max_kl_increase: float = 1.92, n_resam
     Hm = f64(N, K) if R else None
     Hr = f64(R, N, K) if R and keep_resamples else None
     ms = (c_double * 4)()
-    _i = lambda a: a.ctypes.data_as(_lib._I)  # noqa: E731
-    _d = lambda a: None if a is None or a.size == 0 else _ptr(a)  # noqa: E731
+    p = _lib.pointer
     _lib.check(lib.salnmf_assign_signatures(
-        int(device), _ptr(X), N, V, _ptr(S), K, R, seed, Q if R else 0, _d(q), min_it, max_it, freq, tol, thr, chunk,
-        _ptr(H), _i(act), _ptr(err), _i(rnd), _ptr(kl), _i(ntr), nit.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), _i(conv),
-        _ptr(Hd), _ptr(err_d), _i(nit_d), _i(conv_d), _d(sel), _d(Hq), _d(Hm), _d(Hr), ctypes.cast(ms, _lib._D),
+        int(device), p(X), N, V, p(S), K, R, seed, Q if R else 0, p(q), min_it, max_it, freq, tol, thr, chunk,
+        p(H), p(act), p(err), p(rnd), p(kl), p(ntr), p(nit), p(conv), p(Hd), p(err_d), p(nit_d), p(conv_d), p(sel), p(Hq), p(Hm), p(Hr),
+        ctypes.cast(ms, _lib._D),
     ))
     timings = {"resample_s": ms[0] / 1e3, "assign_s": ms[1] / 1e3, "reduce_s": ms[2] / 1e3, "assign_kernel_ms": ms[1],
                "n_chunks": int(ms[3]), "total_s": time.perf_counter() - t_start}

@@ -19,7 +19,6 @@ import numpy as np
 
 from . import _lib
 from .anndata_compat import ANNDATA_TYPES
-from .engine import _ptr
 from .initialization import check_given_asignatures
 from .resample import check_counts, check_seed
 
@@ -126,9 +125,7 @@ def refit_exposures(counts, signatures, n_resamples: int = 0, resample_seed: int
     X, S, R, seed, min_it, max_it, freq, tol, q, chunk = check_arguments(counts, signatures, n_resamples, resample_seed, quantiles, min_iterations,
                                                                          max_iterations, conv_test_freq, tol, chunk_bytes)
     (N, V), K = X.shape, S.shape[0]
-    lib = _lib.load()
-    if lib.salnmf_device_count() < 1:
-        raise _lib.EngineUnavailable("no HIP device visible: salamander_amd runs on MI355X (gfx950) only and has no CPU fallback.")
+    lib = _lib.load_with_device()
 
     Q = int(q.size)
     H = np.empty((N, K), dtype=np.float64)
@@ -141,11 +138,10 @@ def refit_exposures(counts, signatures, n_resamples: int = 0, resample_seed: int
     err_r = np.empty((R, N), dtype=np.float64) if R else None
     Hr = np.empty((R, N, K), dtype=np.float64) if R and keep_resamples else None
     ms = (c_double * 4)()
-    _i = lambda a: None if a is None else a.ctypes.data_as(_lib._I)  # noqa: E731
-    _d = lambda a: None if a is None or a.size == 0 else _ptr(a)  # noqa: E731
+    p = _lib.pointer
     _lib.check(lib.salnmf_refit_exposures(
-        int(device), _ptr(X), N, V, _ptr(S), K, R, seed, Q if R else 0, _d(q), min_it, max_it, freq, tol, chunk,
-        _ptr(H), _ptr(err), _i(nit), _i(conv), _d(Hq), _d(Hm), _i(nit_r), _d(err_r), _d(Hr), ctypes.cast(ms, _lib._D),
+        int(device), p(X), N, V, p(S), K, R, seed, Q if R else 0, p(q), min_it, max_it, freq, tol, chunk,
+        p(H), p(err), p(nit), p(conv), p(Hq), p(Hm), p(nit_r), p(err_r), p(Hr), ctypes.cast(ms, _lib._D),
     ))
     timings = {"resample_s": ms[0] / 1e3, "refit_s": ms[1] / 1e3, "reduce_s": ms[2] / 1e3, "refit_kernel_ms": ms[1],
                "n_chunks": int(ms[3]), "total_s": time.perf_counter() - t_start}
