@@ -474,6 +474,41 @@ int salnmf_batch_download_dataset(salnmf_batch* b, int dataset, int raw, double*
  * alone between two events -> average milliseconds per launch.  The slots hold the same resamples afterwards. */
 int salnmf_profile_resample(salnmf_batch* b, int n_resamples, uint64_t seed, int n_calls, double* avg_ms);
 
+/* ---- Count splitting (Poisson thinning) of a count matrix, drawn on the device (csrc/salnmf_split.h).
+ * X as for the resampler: non-negative integer values, row totals T_n < 2^32.  Every single mutation goes to the training
+ * matrix with probability thr / 2^64, independently; for Poisson counts the two halves are independent Poisson counts:
+ *   thr = (uint64) floor(train_fraction * 2^64), 1 <= thr <= 2^64 - 1 (the fraction itself never crosses this boundary);
+ *   mutation j of row n (0 <= j < T_n) belongs to cell v(j), the smallest v with cum[v] > j, cum[v] = sum_{w <= v} X[n, w];
+ *   generator: Philox4x32-10, key = (seed & 0xffffffff, seed >> 32);
+ *   block q of row n of split f: counter (q, 0x53504C54, n, f) -> words (o0, o1, o2, o3) -- the resampler's second counter
+ *   word is always 0, so the two streams never meet under one seed;
+ *   draw 2q uses u = o0 | o1 << 32, draw 2q + 1 uses u = o2 | o3 << 32; draws j >= T_n are discarded;
+ *   mutation j goes to train iff u_j < thr.
+ * train_f[n, v] counts the mutations of cell v sent to train, test_f[n, v] = X[n, v] - train_f[n, v].  Integer arithmetic
+ * throughout: the same bits on every run, zero cells stay zero in both halves, split f does not depend on n_splits.  The
+ * entry points refuse, before any launch, what the resampler refuses, thr == 0 and n_splits outside [1, 32767]. */
+/* Stand-alone: upload, draw, download.  n_features <= 3072.  train_out, test_out: n_splits x n_samples x n_features each,
+ * plain counts. */
+int salnmf_split_counts(int device, const double* X, int64_t n_samples, int n_features, int n_splits, uint64_t thr, uint64_t seed,
+                        double* train_out, double* test_out);
+/* n_splits splits of the batch's uploaded X (salnmf_batch_upload_X first) into 2 n_splits slots in X's own layout -- pad rows
+ * and columns 0, entries max(count, SALNMF_EPSILON) -- each with its x log x constants: train split f is dataset f, test
+ * split f dataset n_splits + f, for salnmf_batch_set_dataset, _download_dataset and _heldout_kl.  A second call, or another
+ * upload of X, drops the slots and puts every member back on dataset -1.  Splits and resamples exclude each other on one
+ * batch: with resamples drawn this call is refused, and salnmf_batch_resample is refused once a split is drawn (upload X
+ * again to drop either). */
+int salnmf_batch_split(salnmf_batch* b, int n_splits, uint64_t thr, uint64_t seed);
+/* Held-out scoring: samplewise_kl_divergence of member members[i] against dataset datasets[i] instead of its own, with its
+ * exposures read as max(scale * H, EPSILON) -> out (n_members x n_samples).  The forward pass's per-sample mode, unchanged,
+ * on the engine's grid for the shape: the bits an engine holding that dataset, the member's W and the scaled, clipped H
+ * computes (salnmf_samplewise_kl).  For a member fitted on train split f, dataset n_splits + f and
+ * scale = (1 - train_fraction) / train_fraction give the out-of-sample Poisson deviance.  The members' own state, datasets
+ * included, is left as it is.  members: each at most once; scale positive and finite. */
+int salnmf_batch_heldout_kl(salnmf_batch* b, int n_members, const int* members, const int* datasets, double scale, double* out);
+/* Development aid (tools/bench_split.py): salnmf_batch_split once, then n_calls launches of the split kernel alone between
+ * two events -> average milliseconds per launch.  The slots hold the same splits afterwards. */
+int salnmf_profile_split(salnmf_batch* b, int n_splits, uint64_t thr, uint64_t seed, int n_calls, double* avg_ms);
+
 /* ---- Signature stability: match, cluster and score the signatures of many fits (csrc/salnmf_stability.h, DESIGN.md
  * section 12 "Stability").  A group is M >= 2 signature matrices of one shape K x V (K <= 16, V <= 96) and one error value
  * per member (errors == NULL: all zero).  Per group: rows are scaled to unit Euclidean norm; the member of smallest error

@@ -13,8 +13,9 @@ from .assign import AssignResult, assign_signatures
 from .engine import Engine
 from .refit import RefitResult, refit_exposures
 from .resample import resample_counts
+from .split import split_counts
 from .stability import signature_stability
 
 __version__ = "0.1.0"
 __all__ = ["models", "Engine", "AnnData", "MuData", "EngineUnavailable", "resample_counts", "signature_stability", "refit_exposures", "RefitResult", "assign_signatures",
-           "AssignResult"]
+           "AssignResult", "split_counts"]

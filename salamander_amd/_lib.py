@@ -122,6 +122,11 @@ SIGNATURES = {
     "salnmf_batch_set_dataset": (c_int, [_P, c_int, c_int]),
     "salnmf_batch_download_dataset": (c_int, [_P, c_int, c_int, _D]),
     "salnmf_profile_resample": (c_int, [_P, c_int, c_uint64, c_int, _D]),
+    # count splitting and held-out scoring: salamander_amd/split.py, batch.py
+    "salnmf_split_counts": (c_int, [c_int, _D, c_int64, c_int, c_int, c_uint64, c_uint64, _D, _D]),
+    "salnmf_batch_split": (c_int, [_P, c_int, c_uint64, c_uint64]),
+    "salnmf_batch_heldout_kl": (c_int, [_P, c_int, _I, _I, c_double, _D]),
+    "salnmf_profile_split": (c_int, [_P, c_int, c_uint64, c_uint64, c_int, _D]),
     # signature stability: salamander_amd/stability.py, batch.py
     "salnmf_batch_stability": (c_int, [_P, c_int, _I, _I, _D, c_int, _I, _I, _I, _D, _D, _D, _D, _D, _D, _D]),
     "salnmf_signature_stability": (c_int, [c_int, _D, c_int, _I, _I, c_int, _D, c_int, _I, _I, _I, _D, _D, _D, _D, _D, _D, _D]),

@@ -15,6 +15,7 @@ import numpy as np
 from . import _lib
 from .engine import _as_c, _ptr
 from .resample import check_n_resamples, check_seed
+from .split import check_n_splits, heldout_scale, train_threshold
 from .stability import _Outputs, check_errors, check_group_shape, check_max_rounds
 
 SLOTS = _lib.BATCH_SLOTS
@@ -48,6 +49,7 @@ class BatchEngine:
         _lib.check(self._lib.salnmf_batch_create(self.device, self.V, self.N, self.M, _iptr(ks), ctypes.byref(handle)))
         self._handle = handle
         self.R = 0  # resamples of X on the device
+        self.F = 0  # count splits of X on the device (datasets 0 .. F - 1 train, F .. 2 F - 1 test)
 
     @property
     def _h(self):
@@ -70,7 +72,7 @@ class BatchEngine:
     def upload_X(self, X, clip: bool = False):
         X = _as_c(X, (self.N, self.V), "X")
         _lib.check(self._lib.salnmf_batch_upload_X(self._h, _ptr(X), int(bool(clip))))
-        self.R = 0  # (the resamples go with the X they were drawn from)
+        self.R = self.F = 0  # (the resamples and splits go with the X they were drawn from)
 
     def resample(self, n_resamples: int, seed: int = 0):
         """Draw ``n_resamples`` bootstrap resamples of the uploaded X on the device (``resample.py``): datasets
@@ -80,8 +82,36 @@ class BatchEngine:
         _lib.check(self._lib.salnmf_batch_resample(self._h, R, seed))
         self.R = R
 
+    def split(self, n_splits: int, train_fraction: float = 0.5, seed: int = 0):
+        """Draw ``n_splits`` count splits of the uploaded X on the device (``split.py``): train split f is dataset f, test
+        split f dataset ``n_splits + f``, dataset -1 being X itself.  Every member is back on dataset -1.  A batch holds
+        splits or resamples, not both."""
+        F, thr, seed = check_n_splits(n_splits), train_threshold(train_fraction), check_seed(seed)
+        _lib.check(self._lib.salnmf_batch_split(self._h, F, thr, seed))
+        self.F, self.R = F, 0
+
+    def heldout_kl(self, members, datasets, train_fraction: float = 0.5) -> np.ndarray:
+        """Per-sample KL divergences of ``members[i]`` against dataset ``datasets[i]`` instead of its own, its exposures
+        scaled by ``(1 - train_fraction) / train_fraction`` and clipped: ``(len(members), N)``.  The members keep their
+        datasets."""
+        train_threshold(train_fraction)
+        m, d = _ints(members), _ints(datasets)
+        if m.shape != d.shape:
+            raise ValueError("'members' and 'datasets' must have the same length.")
+        out = np.empty((len(m), self.N), dtype=np.float64)
+        _lib.check(self._lib.salnmf_batch_heldout_kl(self._h, len(m), _iptr(m), _iptr(d), heldout_scale(train_fraction), _ptr(out)))
+        return out
+
+    def profile_split(self, n_splits: int, train_fraction: float = 0.5, seed: int = 0, n_calls: int = 20) -> float:
+        """Development aid: average milliseconds of the split kernel alone, by device events."""
+        ms = c_double(0.0)
+        F, thr = check_n_splits(n_splits), train_threshold(train_fraction)
+        _lib.check(self._lib.salnmf_profile_split(self._h, F, thr, check_seed(seed), int(n_calls), ctypes.byref(ms)))
+        self.F, self.R = F, 0
+        return float(ms.value)
+
     def set_dataset(self, member: int, dataset: int):
-        """The matrix ``member`` fits from now on: resample ``dataset``, or -1 for the uploaded X (the default)."""
+        """The matrix ``member`` fits from now on: resample (or split half) ``dataset``, or -1 for the uploaded X (the default)."""
         _lib.check(self._lib.salnmf_batch_set_dataset(self._h, int(member), int(dataset)))
 
     def download_dataset(self, dataset: int, raw: bool = False) -> np.ndarray:

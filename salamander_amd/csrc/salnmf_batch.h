@@ -5,6 +5,7 @@
 //   X    [Np][96]       the uploaded matrix, clipped and padded as an engine holds it (salnmf_kernels.h)
 //   xlx  [Np][16]       its x-only KL constants (the forward pass's mode 0), once per upload of X
 //   Xr   [R][Np][96], xlxr [R][Np][16]   the resamples in the same layout (salnmf_resample.h writes them in place)
+//        or, after salnmf_batch_split, 2 F slots: train split f in slot f, test split f in slot F + f (salnmf_split.h)
 //   every member reads ONE dataset, through the X / xlx pointers of its BatchMember (the uploaded X until
 //   salnmf_batch_set_dataset says otherwise)
 //   per member m:  W [K_m][V], H [Np][16] (pad columns 0, pad rows 1 -- an engine's H for K <= 16), G [K_m][V] (the last

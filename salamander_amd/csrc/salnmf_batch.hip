@@ -1,13 +1,14 @@
 // KLNMFSweep on the device: the batch handle of include/salnmf.h (salnmf_batch_*), the batched objective / per-sample
 // divergence passes, and the host side of the batched step (its kernel: salnmf_small.hip, small_kl_batch_kernel).
 // Layout and the bit-for-bit argument: salnmf_batch.h, DESIGN.md section 12.  Also the host side of the bootstrap resampler
-// (salnmf_resample.h) and of the signature-stability kernel (salnmf_stability.h).
+// (salnmf_resample.h), of count splitting (salnmf_split.h) and of the signature-stability kernel (salnmf_stability.h).
 #define SALNMF_TEMPLATES_ONLY 1
 #include "../../include/salnmf.h"
 #include "salnmf_batch.h"
 #include "salnmf_error.h"
 #include "salnmf_refit.h"
 #include "salnmf_resample.h"
+#include "salnmf_split.h"
 #include "salnmf_stability.h"
 
 #include <algorithm>
@@ -30,6 +31,11 @@ struct BatchFwdArgs {
     double* sum_out;                    // mode 0: row `slot` of the objective array, [n_members] (pinned host memory)
     int64_t N, ntiles;
     int V;
+    // held-out scoring (salnmf_batch_heldout_kl), null for every other launch: entry blockIdx.y of `xover` is the
+    // [Np][96] matrix the member is evaluated against instead of its own dataset, and `hscale` ([16], mode 1 only) the
+    // exposure scale H is read with, as clip(H * hscale)
+    const double* const* __restrict__ xover;
+    const double* __restrict__ hscale;
 };
 
 // forward_body<KS, MODE> (salnmf_forward_kernel.h) for one member with the parameters an engine of <= 16 signatures and
@@ -44,7 +50,8 @@ __global__ void __launch_bounds__(BLOCK, 2) batch_forward_kernel(BatchFwdArgs a)
     const int m = a.active[blockIdx.y];
     const BatchMember& b = a.members[m];
     FwdParams p{};
-    p.X = b.X;
+    p.X = a.xover ? a.xover[blockIdx.y] : b.X;
+    if (MODE == 1) p.hscale = a.hscale;
     p.H = b.H;
     p.W = b.W;
     p.xlx = b.xlx;  // [Np][16] (mode 0)
@@ -88,7 +95,8 @@ struct salnmf_batch {
     // dataset each member reads (-1: the uploaded X); the device's member table is rewritten before the next launch
     std::vector<double> hostX;  // [N][V] as uploaded, unclipped
     double *Xr = nullptr, *xlxr = nullptr;
-    int R = 0;
+    int R = 0;  // slots: the resamples, or 2 F after a split
+    int F = 0;  // count splitting (salnmf_batch_split): train split f is dataset f, test split f dataset F + f
     std::vector<int> dataset;
     bool members_dirty = false;
 };
@@ -117,7 +125,7 @@ static void drop_resamples(salnmf_batch* b) {
     if (b->Xr) (void)hipFree(b->Xr);
     if (b->xlxr) (void)hipFree(b->xlxr);
     b->Xr = b->xlxr = nullptr;
-    b->R = 0;
+    b->R = b->F = 0;
 }
 
 // Counts a resample can be drawn from: integer values, none negative, row totals below 2^32.  The counts as uint32.
@@ -140,6 +148,13 @@ static int check_counts(const double* X, int64_t N, int V, std::vector<uint32_t>
 static int check_resample_args(int n_resamples) {
     // (one workgroup per (row, resample): the resample is the grid's y)
     if (n_resamples < 1 || n_resamples > 65535) return fail("n_resamples must be in [1, 65535], got %d", n_resamples);
+    return 0;
+}
+
+static int check_split_args(int n_splits, uint64_t thr) {
+    // (one workgroup per (row, split), two slots per split: the split is the grid's y)
+    if (n_splits < 1 || n_splits > 32767) return fail("n_splits must be in [1, 32767], got %d", n_splits);
+    if (thr == 0) return fail("the train threshold must be in [1, 2^64 - 1]: train_fraction * 2^64 rounds to 0");
     return 0;
 }
 
@@ -506,6 +521,7 @@ int salnmf_batch_resample(salnmf_batch* b, int n_resamples, uint64_t seed) {
     if (!b) return fail("null batch");
     if (!b->x_ok) return fail("upload X first");
     CK(check_resample_args(n_resamples));
+    if (b->F) return fail("this batch holds %d count splits: resamples and splits exclude each other on one batch (upload X again to drop them)", b->F);
     std::vector<uint32_t> counts;
     CK(check_counts(b->hostX.data(), b->N, b->V, counts));
     HIPCK(hipSetDevice(b->device));
@@ -535,9 +551,83 @@ int salnmf_batch_resample(salnmf_batch* b, int n_resamples, uint64_t seed) {
     return cleanup(0);
 }
 
+int salnmf_batch_split(salnmf_batch* b, int n_splits, uint64_t thr, uint64_t seed) {
+    if (!b) return fail("null batch");
+    if (!b->x_ok) return fail("upload X first");
+    CK(check_split_args(n_splits, thr));
+    if (b->R && !b->F) return fail("this batch holds %d resamples: resamples and splits exclude each other on one batch (upload X again to drop them)", b->R);
+    std::vector<uint32_t> counts;
+    CK(check_counts(b->hostX.data(), b->N, b->V, counts));
+    HIPCK(hipSetDevice(b->device));
+    HIPCK(hipStreamSynchronize(b->stream));
+    drop_resamples(b);
+    uint32_t* dcounts = nullptr;
+    auto cleanup = [&](int rc) {
+        if (dcounts) (void)hipFree(dcounts);
+        if (rc) drop_resamples(b);
+        return rc;
+    };
+    const size_t xsz = (size_t)b->Np * VMAX, csz = (size_t)b->Np * 16;
+    const int slots = 2 * n_splits;
+    if (hipMalloc(&b->Xr, (size_t)slots * xsz * sizeof(double)) != hipSuccess || hipMalloc(&b->xlxr, (size_t)slots * csz * sizeof(double)) != hipSuccess ||
+        hipMalloc(&dcounts, counts.size() * sizeof(uint32_t)) != hipSuccess)
+        return cleanup(fail("hipMalloc failed (%d splits)", n_splits));
+    b->R = slots;
+    b->F = n_splits;
+    if (hipMemcpyAsync(dcounts, counts.data(), counts.size() * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream) != hipSuccess)
+        return cleanup(fail("hipMemcpy failed"));
+    // straight into the slots, in X's layout: train split f is slot f, test split f slot F + f
+    launch_split(SplitArgs{dcounts, b->Xr, b->Xr + (size_t)n_splits * xsz, b->N, b->Np, b->V, VMAX, (uint32_t)seed, (uint32_t)(seed >> 32), thr, SALNMF_EPSILON},
+                 n_splits, b->stream);
+    if (hipGetLastError() != hipSuccess) return cleanup(fail("split launch failed"));
+    for (int s = 0; s < slots; ++s) {
+        launch_xlogx_lane(b->Xr + (size_t)s * xsz, b->Np, b->V, b->xlxr + (size_t)s * csz, b->stream);
+        if (hipGetLastError() != hipSuccess) return cleanup(fail("xlogx launch failed"));
+    }
+    if (hipStreamSynchronize(b->stream) != hipSuccess) return cleanup(fail("split failed on the device"));
+    return cleanup(0);
+}
+
+int salnmf_batch_heldout_kl(salnmf_batch* b, int n_members, const int* members, const int* datasets, double scale, double* out) {
+    if (!b) return fail("null batch");
+    if (!out || !datasets) return fail("null argument");
+    CK(check_list(b, n_members, members));
+    if (n_members < 1) return fail("held-out scoring needs at least one member");
+    if (!b->x_ok) return fail("upload X first");
+    if (!(scale > 0.0) || !std::isfinite(scale)) return fail("the exposure scale must be positive and finite, got %g", scale);
+    // (host buffers of the asynchronous copies: declared before d, so they outlive its wait for the stream)
+    std::vector<const double*> xs((size_t)n_members);
+    for (int i = 0; i < n_members; ++i) {
+        if (datasets[i] < -1 || datasets[i] >= b->R)
+            return fail("dataset %d out of range (%d resamples or split halves; -1 is the uploaded X)", datasets[i], b->R);
+        xs[(size_t)i] = datasets[i] < 0 ? b->X : b->Xr + (size_t)datasets[i] * b->Np * VMAX;
+    }
+    const std::vector<double> hs(16, scale);
+    std::vector<double> host((size_t)b->M * b->Np);
+    HIPCK(hipSetDevice(b->device));
+    CK(set_list(b, b->dobj, b->obj_list, std::vector<int>(members, members + n_members)));
+    CK(flush_members(b));
+    DevBufs d(b->stream);
+    const double** dxs = d.get<const double*>(xs.size());
+    double* dhs = d.get<double>(hs.size());
+    if (!dxs || !dhs) return fail("hipMalloc failed (held-out scoring of %d members)", n_members);
+    HIPCK(hipMemcpyAsync(dxs, xs.data(), xs.size() * sizeof(double*), hipMemcpyHostToDevice, b->stream));
+    HIPCK(hipMemcpyAsync(dhs, hs.data(), hs.size() * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    BatchFwdArgs a{b->dmembers, b->dobj, b->klout, nullptr, nullptr, b->N, b->ntiles, b->V, dxs, dhs};
+    hipLaunchKernelGGL(batch_forward_kernel<1>, dim3(b->fgrid, n_members), dim3(BLOCK), 0, b->stream, a);
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpyAsync(host.data(), b->klout, host.size() * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    HIPCK(hipStreamSynchronize(b->stream));
+    for (int i = 0; i < n_members; ++i) {
+        const double* src = host.data() + (size_t)members[i] * b->Np;
+        std::copy(src, src + b->N, out + (size_t)i * b->N);
+    }
+    return 0;
+}
+
 int salnmf_batch_set_dataset(salnmf_batch* b, int member, int dataset) {
     CK(check_member(b, member));
-    if (dataset < -1 || dataset >= b->R) return fail("dataset %d out of range (%d resamples; -1 is the uploaded X)", dataset, b->R);
+    if (dataset < -1 || dataset >= b->R) return fail("dataset %d out of range (%d resamples or split halves; -1 is the uploaded X)", dataset, b->R);
     if (b->dataset[(size_t)member] != dataset) point_member(b, member, dataset);
     return 0;
 }
@@ -545,7 +635,7 @@ int salnmf_batch_set_dataset(salnmf_batch* b, int member, int dataset) {
 int salnmf_batch_download_dataset(salnmf_batch* b, int dataset, int raw, double* out) {
     if (!b || !out) return fail("null argument");
     if (!b->x_ok) return fail("upload X first");
-    if (dataset < -1 || dataset >= b->R) return fail("dataset %d out of range (%d resamples; -1 is the uploaded X)", dataset, b->R);
+    if (dataset < -1 || dataset >= b->R) return fail("dataset %d out of range (%d resamples or split halves; -1 is the uploaded X)", dataset, b->R);
     HIPCK(hipSetDevice(b->device));
     const double* src = dataset < 0 ? b->X : b->Xr + (size_t)dataset * b->Np * VMAX;
     if (raw) {
@@ -592,6 +682,70 @@ int salnmf_resample_counts(int device, const double* X, int64_t n_samples, int n
     launch_resample(ResampleArgs{dcounts, dout, n_samples, n_samples, n_features, n_features, (uint32_t)seed, (uint32_t)(seed >> 32), 0.0}, n_resamples, nullptr);
     if (hipGetLastError() != hipSuccess) return cleanup(fail("resample launch failed"));
     if (hipMemcpy(out, dout, nout * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return cleanup(fail("resample failed on the device"));
+    return cleanup(0);
+}
+
+int salnmf_split_counts(int device, const double* X, int64_t n_samples, int n_features, int n_splits, uint64_t thr, uint64_t seed, double* train_out,
+                        double* test_out) {
+    if (!X || !train_out || !test_out) return fail("null argument");
+    if (n_samples < 1 || n_samples > 0x7fffffff) return fail("n_samples must be in [1, 2^31), got %lld", (long long)n_samples);
+    if (n_features < 1 || n_features > RESAMPLE_VMAX) return fail("n_features must be in [1, %d], got %d", RESAMPLE_VMAX, n_features);
+    CK(check_split_args(n_splits, thr));
+    std::vector<uint32_t> counts;
+    CK(check_counts(X, n_samples, n_features, counts));
+    int ndev = 0;
+    HIPCK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail("device %d out of range (%d visible)", device, ndev);
+    HIPCK(hipSetDevice(device));
+    hipDeviceProp_t prop;
+    HIPCK(hipGetDeviceProperties(&prop, device));
+    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0) return fail("this build targets gfx950 only; device %d is %s", device, prop.gcnArchName);
+    uint32_t* dcounts = nullptr;
+    double* dout = nullptr;  // train | test
+    auto cleanup = [&](int rc) {
+        if (dcounts) (void)hipFree(dcounts);
+        if (dout) (void)hipFree(dout);
+        return rc;
+    };
+    const size_t nout = (size_t)n_splits * counts.size();
+    if (hipMalloc(&dcounts, counts.size() * sizeof(uint32_t)) != hipSuccess || hipMalloc(&dout, 2 * nout * sizeof(double)) != hipSuccess)
+        return cleanup(fail("hipMalloc failed (%d splits of %lld x %d)", n_splits, (long long)n_samples, n_features));
+    if (hipMemcpy(dcounts, counts.data(), counts.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return cleanup(fail("hipMemcpy failed"));
+    launch_split(SplitArgs{dcounts, dout, dout + nout, n_samples, n_samples, n_features, n_features, (uint32_t)seed, (uint32_t)(seed >> 32), thr, 0.0}, n_splits,
+                 nullptr);
+    if (hipGetLastError() != hipSuccess) return cleanup(fail("split launch failed"));
+    if (hipMemcpy(train_out, dout, nout * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(test_out, dout + nout, nout * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+        return cleanup(fail("split failed on the device"));
+    return cleanup(0);
+}
+
+int salnmf_profile_split(salnmf_batch* b, int n_splits, uint64_t thr, uint64_t seed, int n_calls, double* avg_ms) {
+    if (!b || !avg_ms) return fail("null argument");
+    if (!b->x_ok) return fail("upload X first");
+    if (n_calls < 1) return fail("n_calls must be positive");
+    CK(salnmf_batch_split(b, n_splits, thr, seed));  // (validates, allocates the slots, warms the kernel up)
+    std::vector<uint32_t> counts;
+    CK(check_counts(b->hostX.data(), b->N, b->V, counts));
+    uint32_t* dcounts = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto cleanup = [&](int rc) {
+        if (dcounts) (void)hipFree(dcounts);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        return rc;
+    };
+    if (hipMalloc(&dcounts, counts.size() * sizeof(uint32_t)) != hipSuccess || hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)
+        return cleanup(fail("hipMalloc failed"));
+    if (hipMemcpy(dcounts, counts.data(), counts.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return cleanup(fail("hipMemcpy failed"));
+    const SplitArgs a{dcounts, b->Xr, b->Xr + (size_t)n_splits * b->Np * VMAX, b->N, b->Np, b->V, VMAX, (uint32_t)seed, (uint32_t)(seed >> 32), thr, SALNMF_EPSILON};
+    (void)hipEventRecord(e0, b->stream);
+    for (int i = 0; i < n_calls; ++i) launch_split(a, n_splits, b->stream);  // (the same bits every time)
+    (void)hipEventRecord(e1, b->stream);
+    if (hipGetLastError() != hipSuccess || hipEventSynchronize(e1) != hipSuccess) return cleanup(fail("split failed on the device"));
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    *avg_ms = (double)ms / n_calls;
     return cleanup(0);
 }
 

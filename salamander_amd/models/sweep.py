@@ -19,6 +19,12 @@ member (K, seed, r) fits resample r, and every member still equals the single fi
 field does with such fits -- keep the largest K whose signatures come back the same -- is ``stability=True``: for every K
 the signatures of all its members are matched to each other, clustered into consensus signatures and scored by their
 silhouettes on the device (``stability.py``), and ``suggest_n_signatures`` applies the customary thresholds.
+
+``n_splits=F`` adds the second criterion, held-out likelihood by count splitting (``split.py``): the counts are thinned F
+times on the device into independent train and test halves, member (K, seed, f) fits ``train_splits_[f]`` -- again bit for
+bit the single fit on that matrix -- and is scored against ``test_splits_[f]`` with its exposures scaled by
+``(1 - p) / p``, all batched members in one launch of the forward pass (``BatchEngine.heldout_kl``).
+``suggest_n_signatures_heldout`` returns the K of smallest mean held-out divergence.
 """
 
 from __future__ import annotations
@@ -31,11 +37,13 @@ import numpy as np
 from ..anndata_compat import ANNDATA_TYPES
 from ..batch import MAX_FEATURES, MAX_SAMPLES, MAX_SIGNATURES, SLOTS, BatchEngine
 from ..initialization import INIT_METHODS, check_given_asignatures
+from ..engine import Engine
 from ..resample import check_counts, check_n_resamples, check_seed, resample_counts
+from ..split import check_n_splits, heldout_scale, split_counts, train_threshold
 from ..stability import MAX_FEATURES as STABILITY_MAX_FEATURES
 from ..stability import MAX_SIGNATURES as STABILITY_MAX_SIGNATURES
 from ..stability import check_max_rounds, signature_stability
-from ..utils import type_checker, value_checker
+from ..utils import EPSILON, type_checker, value_checker
 from .klnmf import KLNMF
 from .signature_nmf import SignatureNMF
 
@@ -61,7 +69,20 @@ class KLNMFSweep:
     ``stability_converged_``; ``timings_["stability_s"]`` is the time it took.  A K the kernel cannot take (more than 16
     signatures, or more than 96 features) gets NaN scores, ``None`` for its arrays, 0 rounds and ``False``.
     ``suggest_n_signatures`` picks the largest K that passes the thresholds; it raises ``ValueError`` on a sweep built
-    without ``stability=True`` and returns ``None`` before ``fit`` (the scores are NaN until then)."""
+    without ``stability=True`` and returns ``None`` before ``fit`` (the scores are NaN until then).
+
+    With ``n_splits = F >= 1`` (not together with ``n_resamples``) the counts are split F times by thinning: every
+    mutation goes to ``train_splits_[f]`` with probability ``train_fraction`` and to ``test_splits_[f]`` otherwise (both
+    ``(F, N, V)``, drawn from ``split_seed``).  The members are K-major, seed-middle, split-minor, member (K, seed, f) fits
+    ``train_splits_[f]``; ``split_of_`` holds f per member (-1 without splits) and ``reconstruction_errors_`` (the training
+    error) is ``(len(ns_signatures), max(1, len(seeds)), F)``.  Each model's ``adata.obs["heldout_error"]`` is its
+    per-sample KL divergence to ``max(test_splits_[f], EPSILON)`` with the exposures ``max(c H, EPSILON)``,
+    ``c = (1 - train_fraction) / train_fraction``; ``heldout_errors_`` holds the sums, shaped like
+    ``reconstruction_errors_``.  For every (K, f) the seed of smallest training error (lowest index on ties) is taken --
+    nothing of the test half enters the selection -- and ``heldout_mean_`` / ``heldout_sem_`` ``(len(ns_signatures),)``
+    are the mean of its held-out error over f and ``std(ddof=1) / sqrt(F)`` (NaN at F = 1).
+    ``timings_["split_s"]`` and ``timings_["heldout_s"]`` are the time of the draw and of the scoring.  With
+    ``stability=True`` the members of a K count as seeds x splits."""
 
     def __init__(
         self,
@@ -79,6 +100,9 @@ class KLNMFSweep:
         resample_seed: int = 0,
         stability: bool = False,
         stability_max_rounds: int = 20,
+        n_splits: int = 0,
+        train_fraction: float = 0.5,
+        split_seed: int = 0,
     ):
         ns = list(ns_signatures)
         if not ns or not all(isinstance(k, (int, np.integer)) and not isinstance(k, bool) and k > 0 for k in ns):
@@ -88,11 +112,17 @@ class KLNMFSweep:
         value_checker("init_method", init_method, INIT_METHODS)
         self.n_resamples = check_n_resamples(n_resamples, minimum=0)
         self.resample_seed = check_seed(resample_seed)
+        self.n_splits = check_n_splits(n_splits, minimum=0)
+        train_threshold(train_fraction)
+        self.train_fraction = float(train_fraction)
+        self.split_seed = check_seed(split_seed)
+        if self.n_splits and self.n_resamples:
+            raise ValueError("'n_splits' and 'n_resamples' exclude each other: a sweep fits count splits or bootstrap resamples, not both.")
         self.ns_signatures = [int(k) for k in ns]
         self.seeds = None if not seeds else [int(s) for s in seeds]
         self.stability = bool(stability)
         self.stability_max_rounds = check_max_rounds(stability_max_rounds)
-        if self.stability and max(1, len(self.seeds or [])) * max(1, self.n_resamples) < 2:
+        if self.stability and max(1, len(self.seeds or [])) * max(1, self.n_resamples) * max(1, self.n_splits) < 2:
             raise ValueError("'stability=True' needs at least two members per number of signatures: several seeds, or n_resamples >= 2.")
         self.init_method = init_method
         self.min_iterations = min_iterations
@@ -106,6 +136,13 @@ class KLNMFSweep:
         self.reconstruction_errors_ = np.zeros((0, 0))
         self.resamples_ = None
         self.resample_of_ = np.zeros(0, dtype=int)
+        self.train_splits_ = None
+        self.test_splits_ = None
+        self.split_of_ = np.zeros(0, dtype=int)
+        self.heldout_errors_ = np.zeros((0, 0, 0))
+        self.heldout_mean_ = np.full(len(self.ns_signatures), np.nan)
+        self.heldout_sem_ = np.full(len(self.ns_signatures), np.nan)
+        self._fitted = False
         self.timings_: dict[str, float] = {}
         self.member_steps_ = 0
         self._clear_stability()
@@ -118,9 +155,10 @@ class KLNMFSweep:
         )
 
     def _members(self, init_kwargs):
-        """``(K, init_kwargs of the member, resample of the member or -1)`` in K-major, seed-middle, resample-minor order."""
+        """``(K, init_kwargs of the member, resample or split of the member or -1)`` in K-major, seed-middle, resample-minor
+        (split-minor) order."""
         base = {} if init_kwargs is None else dict(init_kwargs)
-        resamples = range(self.n_resamples) if self.n_resamples else [-1]
+        resamples = range(self.n_resamples) if self.n_resamples else range(self.n_splits) if self.n_splits else [-1]
         out = []
         for k in self.ns_signatures:
             for kwargs in [base | {"seed": s} for s in self.seeds] if self.seeds else [init_kwargs]:
@@ -128,10 +166,10 @@ class KLNMFSweep:
         return out
 
     def _member_adata(self, adata, r: int):
-        """The member's own copy of the data: the caller's, or resample r under the caller's obs / var names."""
+        """The member's own copy of the data: the caller's, or resample r (train split r) under the caller's obs / var names."""
         own = adata.copy()
         if r >= 0:
-            own.X = self.resamples_[r].copy()
+            own.X = (self.train_splits_ if self.n_splits else self.resamples_)[r].copy()
         return own
 
     @staticmethod
@@ -183,6 +221,47 @@ class KLNMFSweep:
         ok = [k for k, a, b in zip(self.ns_signatures, self.stability_mean_, self.stability_min_) if a >= mean_stability and b >= min_stability]
         return max(ok) if ok else None
 
+    # ------------------------------------------------------------------ held-out likelihood
+    def _heldout_single(self, model: KLNMF, f: int) -> np.ndarray:
+        """A fallback member's per-sample held-out divergences: one engine on the clipped test half with the model's
+        signatures and its scaled, clipped exposures.  For a shape the batch reaches, the bits ``BatchEngine.heldout_kl``
+        gives."""
+        eps = float(EPSILON)
+        X = np.maximum(self.test_splits_[f], eps)
+        H = np.maximum(heldout_scale(self.train_fraction) * np.asarray(model.adata.obsm["exposures"], dtype=np.float64), eps)
+        n_obs, n_vars = X.shape
+        engine = Engine(n_obs, n_vars, model.n_signatures, device=self.device)
+        try:
+            engine.upload_X(X)
+            engine.upload_W(np.asarray(model.asignatures.X, dtype=np.float64))
+            engine.upload_H(H)
+            return np.asarray(engine.samplewise_kl(), dtype=np.float64)
+        finally:
+            engine.close()
+
+    def _summarise_heldout(self, train_errors: np.ndarray, heldout_errors: np.ndarray) -> None:
+        """``heldout_mean_`` / ``heldout_sem_`` from ``(len(ns), seeds, F)`` training and held-out errors: per (K, f) the
+        seed of smallest training error, lowest index on ties."""
+        F = heldout_errors.shape[2]
+        best = np.argmin(train_errors, axis=1)  # (the first of equal minima)
+        chosen = np.take_along_axis(heldout_errors, best[:, None, :], axis=1)[:, 0, :]
+        self.heldout_mean_ = chosen.mean(axis=1)
+        self.heldout_sem_ = chosen.std(axis=1, ddof=1) / np.sqrt(F) if F > 1 else np.full(len(chosen), np.nan)
+
+    def suggest_n_signatures_heldout(self, one_standard_error: bool = False):
+        """The K of ``ns_signatures`` with the smallest ``heldout_mean_`` (the first of equal ones); with
+        ``one_standard_error`` the smallest K whose mean is at most that minimum plus the minimum's ``heldout_sem_`` (the
+        customary rule; with a NaN standard error, at F = 1, the minimiser itself).  None before ``fit``."""
+        if not self.n_splits:
+            raise ValueError("'suggest_n_signatures_heldout' needs a sweep built with 'n_splits' > 0.")
+        if not self._fitted:
+            return None
+        best = int(np.nanargmin(self.heldout_mean_))
+        if not one_standard_error or np.isnan(self.heldout_sem_[best]):
+            return self.ns_signatures[best]
+        bound = self.heldout_mean_[best] + self.heldout_sem_[best]
+        return min(k for k, mean in zip(self.ns_signatures, self.heldout_mean_) if mean <= bound)
+
     # ------------------------------------------------------------------ fit
     def fit(self, adata, given_parameters: dict[str, Any] | None = None, init_kwargs: dict[str, Any] | None = None,
             fitting_kwargs: dict[str, Any] | None = None, history: bool = True) -> list[KLNMF]:
@@ -194,8 +273,8 @@ class KLNMFSweep:
             for k in self.ns_signatures:  # (KLNMF.fit's own check, before any member is touched)
                 check_given_asignatures(given_parameters["asignatures"], adata, k)
         n_obs, n_vars = np.shape(adata.X)
-        R = self.n_resamples
-        counts = check_counts(adata.X) if R else None  # (before anything touches the device)
+        R, F = self.n_resamples, self.n_splits
+        counts = check_counts(adata.X) if R or F else None  # (before anything touches the device)
         members = self._members(init_kwargs)
         in_reach = [n_obs <= MAX_SAMPLES and n_vars <= MAX_FEATURES and k <= MAX_SIGNATURES and k > n_given for k, _, _ in members]
 
@@ -209,8 +288,8 @@ class KLNMFSweep:
                 batch = None  # (a device without the batched kernel: every member takes KLNMF.fit)
         slot_of = {i: j for j, i in enumerate(batch_ids)} if batch is not None else {}
         models: list[KLNMF] = []
-        t_init = t_fallback = t_resample = t_stability = 0.0
-        self.resamples_ = None
+        t_init = t_fallback = t_resample = t_stability = t_split = t_heldout = 0.0
+        self.resamples_ = self.train_splits_ = self.test_splits_ = None
         self._clear_stability()
         try:
             if batch is not None:
@@ -226,6 +305,18 @@ class KLNMFSweep:
                 else:
                     self.resamples_ = resample_counts(counts, R, self.resample_seed, device=self.device)
                 t_resample = time.perf_counter() - ta
+            if F:
+                # the F splits, once: train split f is the batch's dataset f, test split f its dataset F + f
+                ta = time.perf_counter()
+                if batch is not None:
+                    batch.split(F, self.train_fraction, self.split_seed)
+                    self.train_splits_ = np.stack([batch.download_dataset(f) for f in range(F)])
+                    self.test_splits_ = np.stack([batch.download_dataset(F + f) for f in range(F)])
+                    for i, j in slot_of.items():
+                        batch.set_dataset(j, members[i][2])
+                else:
+                    self.train_splits_, self.test_splits_ = split_counts(counts, F, self.train_fraction, self.split_seed, device=self.device)
+                t_split = time.perf_counter() - ta
             # every member in order: initialised (batched) or fitted (fallback) exactly as the tutorial's loop would
             # do it, so that the legacy NumPy RNG of the random methods advances the same way
             for i, (k, kwargs, r) in enumerate(members):
@@ -243,6 +334,10 @@ class KLNMFSweep:
                     model.compute_reconstruction_errors()
                     self._close_engine(model)
                     t_fallback += time.perf_counter() - ta
+                    if F:
+                        ta = time.perf_counter()
+                        model.adata.obs["heldout_error"] = self._heldout_single(model, r)
+                        t_heldout += time.perf_counter() - ta
                 models.append(model)
             tb = time.perf_counter()
             steps = 0
@@ -259,6 +354,13 @@ class KLNMFSweep:
                         model.history["objective_function"] = objectives[j][1:]
                     model.adata.obs["reconstruction_error"] = kl[j]
             t_batched = time.perf_counter() - tb
+            if F and batch is not None:
+                # one launch over all batched members, each against the test half of its own split
+                ta = time.perf_counter()
+                held = batch.heldout_kl(list(slot_of.values()), [F + members[i][2] for i in slot_of], self.train_fraction)
+                for row, i in zip(held, slot_of):
+                    models[i].adata.obs["heldout_error"] = row
+                t_heldout += time.perf_counter() - ta
             if self.stability:
                 ta = time.perf_counter()
                 self._run_stability(batch, slot_of, members, models, n_vars)
@@ -269,14 +371,22 @@ class KLNMFSweep:
         self.models_ = models
         self.batched_ = np.array([i in slot_of for i in range(len(members))], dtype=bool)
         cols = max(1, len(self.seeds or []))
-        shape = (len(self.ns_signatures), cols, R) if R else (len(self.ns_signatures), cols)
+        shape = (len(self.ns_signatures), cols, R or F) if R or F else (len(self.ns_signatures), cols)
         self.reconstruction_errors_ = np.array([m.reconstruction_error for m in models]).reshape(shape)
-        self.resample_of_ = np.array([r for _, _, r in members], dtype=int)
+        self.resample_of_ = np.array([-1 if F else r for _, _, r in members], dtype=int)
+        self.split_of_ = np.array([r if F else -1 for _, _, r in members], dtype=int)
+        if F:
+            self.heldout_errors_ = np.array([float(np.sum(np.asarray(m.adata.obs["heldout_error"]))) for m in models]).reshape(shape)
+            self._summarise_heldout(self.reconstruction_errors_, self.heldout_errors_)
+        self._fitted = True
         self.member_steps_ = steps
         self.timings_ = {"total_s": time.perf_counter() - t0, "init_s": t_init, "batched_s": t_batched, "fallback_s": t_fallback,
                          "resample_s": t_resample}
         if self.stability:
             self.timings_["stability_s"] = t_stability
+        if F:
+            self.timings_["split_s"] = t_split
+            self.timings_["heldout_s"] = t_heldout
         return models
 
     def _next_stop(self, n_iteration: int) -> int:
