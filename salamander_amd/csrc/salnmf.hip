@@ -2,7 +2,7 @@
 // One engine = one GPU = one shard of the sample axis.  All launches go to the
 // engine's own HIP stream; nothing inside a step synchronises with the host.
 #include "../../include/salnmf.h"
-#include "salnmf_error.h"
+#include "salnmf_device.h"
 #include "salnmf_launch.h"
 #include "salnmf_mv_kernels.h"
 #include "salnmf_mv_wide_kernels.h"
@@ -686,14 +686,8 @@ int salnmf_create(int device, int n_features, int64_t n_samples, int n_signature
     if (n_features < 1 || n_features > VMAX * NB_MAX) return fail("n_features must be in [1, %d], got %d", VMAX * NB_MAX, n_features);
     if (n_signatures < 1 || n_signatures > KC * NC_MAX) return fail("n_signatures must be in [1, %d], got %d", KC * NC_MAX, n_signatures);
     if (n_samples < 1) return fail("n_samples must be positive");
-    int ndev = 0;
-    HIPCK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail("device %d out of range (%d visible)", device, ndev);
-    HIPCK(hipSetDevice(device));
     hipDeviceProp_t prop;
-    HIPCK(hipGetDeviceProperties(&prop, device));
-    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
-        return fail("this build targets gfx950 only; device %d is %s", device, prop.gcnArchName);
+    CK(open_device(device, &prop));
 
     salnmf_engine* e = new salnmf_engine();
     e->device = device;

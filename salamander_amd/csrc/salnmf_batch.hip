@@ -1,11 +1,13 @@
 // KLNMFSweep on the device: the batch handle of include/salnmf.h (salnmf_batch_*), the batched objective / per-sample
 // divergence passes, and the host side of the batched step (its kernel: salnmf_small.hip, small_kl_batch_kernel).
-// Layout and the bit-for-bit argument: salnmf_batch.h, DESIGN.md section 12.  Also the host side of the bootstrap resampler
-// (salnmf_resample.h), of count splitting (salnmf_split.h) and of the signature-stability kernel (salnmf_stability.h).
+// Layout and the bit-for-bit argument: salnmf_batch.h, DESIGN.md section 12.  Also the host side of the two count draws --
+// the bootstrap resampler (salnmf_resample.h) and count splitting (salnmf_split.h), which share one kernel body
+// (count_draw_row) and here one driver per job (draw_into_slots, draw_stand_alone, profile_draw: a draw is its argument check
+// and the callable that launches its kernel) -- and of the signature-stability kernel (salnmf_stability.h).
 #define SALNMF_TEMPLATES_ONLY 1
 #include "../../include/salnmf.h"
 #include "salnmf_batch.h"
-#include "salnmf_error.h"
+#include "salnmf_device.h"
 #include "salnmf_refit.h"
 #include "salnmf_resample.h"
 #include "salnmf_split.h"
@@ -110,9 +112,17 @@ static int flush_members(salnmf_batch* b) {
     return 0;
 }
 
+// dataset d of a batch: slot d of the resamples or split halves, -1 the uploaded X
+static const double* dataset_ptr(const salnmf_batch* b, int d) { return d < 0 ? b->X : b->Xr + (size_t)d * b->Np * VMAX; }
+
+static int check_dataset(const salnmf_batch* b, int d) {
+    if (d < -1 || d >= b->R) return fail("dataset %d out of range (%d resamples or split halves; -1 is the uploaded X)", d, b->R);
+    return 0;
+}
+
 static void point_member(salnmf_batch* b, int m, int dataset) {
     BatchMember& mb = b->members[(size_t)m];
-    mb.X = dataset < 0 ? b->X : b->Xr + (size_t)dataset * b->Np * VMAX;
+    mb.X = dataset_ptr(b, dataset);
     mb.xlx = dataset < 0 ? b->xlx : b->xlxr + (size_t)dataset * b->Np * 16;
     b->dataset[(size_t)m] = dataset;
     b->members_dirty = true;
@@ -186,6 +196,103 @@ static int set_list(salnmf_batch* b, int* dev, std::vector<int>& cache, const st
     return 0;
 }
 
+// ---- the count draws (salnmf_resample.h, salnmf_split.h): one driver per job, the draw being the callable that launches it
+
+// The uploaded counts drawn into n_slots fresh datasets.  `launch(dcounts)` queues the kernel that fills b->Xr straight in X's
+// layout: pad rows and columns 0, the N x V block clipped as upload_X(clip = 1) clips.  A failure leaves the batch without slots.
+template <typename Launch>
+static int draw_into_slots(salnmf_batch* b, int n_slots, Launch launch) {
+    // (host buffer of the asynchronous copy: declared before d, so it outlives its wait for the stream)
+    std::vector<uint32_t> counts;
+    CK(check_counts(b->hostX.data(), b->N, b->V, counts));
+    HIPCK(hipSetDevice(b->device));
+    HIPCK(hipStreamSynchronize(b->stream));
+    drop_resamples(b);
+    DevBufs d(b->stream);
+    const size_t xsz = (size_t)b->Np * VMAX, csz = (size_t)b->Np * 16;
+    auto draw = [&]() -> int {
+        uint32_t* dcounts = d.get<uint32_t>(counts.size());
+        if (!dcounts || hipMalloc(&b->Xr, (size_t)n_slots * xsz * sizeof(double)) != hipSuccess ||
+            hipMalloc(&b->xlxr, (size_t)n_slots * csz * sizeof(double)) != hipSuccess)
+            return fail("hipMalloc failed (%d datasets)", n_slots);
+        HIPCK(hipMemcpyAsync(dcounts, counts.data(), counts.size() * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
+        launch(dcounts);
+        HIPCK(hipGetLastError());
+        for (int s = 0; s < n_slots; ++s) {
+            launch_xlogx_lane(b->Xr + (size_t)s * xsz, b->Np, b->V, b->xlxr + (size_t)s * csz, b->stream);
+            HIPCK(hipGetLastError());
+        }
+        HIPCK(hipStreamSynchronize(b->stream));
+        return 0;
+    };
+    const int rc = draw();
+    if (rc) drop_resamples(b);
+    return rc;
+}
+
+// The draws of a stand-alone count matrix, compact and unclipped: `launch(dcounts, dout)` fills dout, and its first n_out
+// doubles go to out0, the next n_out to out1 where there is a second output.
+template <typename Launch>
+static int draw_stand_alone(int device, const double* X, int64_t n_samples, int n_features, int n_draws, double* out0, double* out1, Launch launch) {
+    if (n_samples < 1 || n_samples > 0x7fffffff) return fail("n_samples must be in [1, 2^31), got %lld", (long long)n_samples);
+    if (n_features < 1 || n_features > RESAMPLE_VMAX) return fail("n_features must be in [1, %d], got %d", RESAMPLE_VMAX, n_features);
+    std::vector<uint32_t> counts;
+    CK(check_counts(X, n_samples, n_features, counts));
+    hipDeviceProp_t prop;
+    CK(open_device(device, &prop));
+    DevBufs d;
+    const size_t n_out = (size_t)n_draws * counts.size();
+    uint32_t* dcounts = d.get<uint32_t>(counts.size());
+    double* dout = d.get<double>((out1 ? 2 : 1) * n_out);
+    if (!dcounts || !dout) return fail("hipMalloc failed (%d draws of %lld x %d)", n_draws, (long long)n_samples, n_features);
+    HIPCK(hipMemcpy(dcounts, counts.data(), counts.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    launch(dcounts, dout);
+    HIPCK(hipGetLastError());
+    HIPCK(hipMemcpy(out0, dout, n_out * sizeof(double), hipMemcpyDeviceToHost));
+    if (out1) HIPCK(hipMemcpy(out1, dout + n_out, n_out * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// Development aid: the average milliseconds of one launch of a draw's kernel, by device events.  `draw()` is the batch's own
+// entry point (it validates, allocates the slots and warms the kernel up), `launch(dcounts)` what it queues.
+template <typename Draw, typename Launch>
+static int profile_draw(salnmf_batch* b, int n_calls, double* avg_ms, Draw draw, Launch launch) {
+    if (!b || !avg_ms) return fail("null argument");
+    if (!b->x_ok) return fail("upload X first");
+    if (n_calls < 1) return fail("n_calls must be positive");
+    CK(draw());
+    std::vector<uint32_t> counts;
+    CK(check_counts(b->hostX.data(), b->N, b->V, counts));
+    DevBufs d(b->stream);
+    uint32_t* dcounts = d.get<uint32_t>(counts.size());
+    if (!dcounts) return fail("hipMalloc failed");
+    HIPCK(hipMemcpy(dcounts, counts.data(), counts.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    const hipEvent_t e0 = d.mark();
+    for (int i = 0; i < n_calls; ++i) launch(dcounts);  // (the same bits every time)
+    const hipEvent_t e1 = d.mark();
+    if (!e0 || !e1) return fail("event record failed");
+    HIPCK(hipGetLastError());
+    HIPCK(hipEventSynchronize(e1));
+    float ms = 0.f;
+    HIPCK(hipEventElapsedTime(&ms, e0, e1));
+    *avg_ms = (double)ms / n_calls;
+    return 0;
+}
+
+// what the batch queues for its draws: resample r into slot r; train split f into slot f, test split f into slot F + f
+static auto batch_resample_launch(salnmf_batch* b, int n_resamples, uint64_t seed) {
+    return [=](const uint32_t* dcounts) {
+        launch_resample(ResampleArgs{dcounts, b->Xr, b->N, b->Np, b->V, VMAX, (uint32_t)seed, (uint32_t)(seed >> 32), SALNMF_EPSILON}, n_resamples, b->stream);
+    };
+}
+
+static auto batch_split_launch(salnmf_batch* b, int n_splits, uint64_t thr, uint64_t seed) {
+    return [=](const uint32_t* dcounts) {
+        double* test = b->Xr + (size_t)n_splits * b->Np * VMAX;
+        launch_split(SplitArgs{dcounts, b->Xr, test, b->N, b->Np, b->V, VMAX, (uint32_t)seed, (uint32_t)(seed >> 32), thr, SALNMF_EPSILON}, n_splits, b->stream);
+    };
+}
+
 // ---- the resampler as salnmf_refit.hip uses it (salnmf_refit.h): this translation unit holds resample_counts_kernel
 int salnmf::refit_check_counts(const double* X, int64_t N, int V, std::vector<uint32_t>& counts) { return check_counts(X, N, V, counts); }
 
@@ -200,27 +307,6 @@ namespace {
 struct StabOut {
     int *assignments, *n_rounds, *converged;
     double *consensus, *a, *b, *silhouette, *cluster, *stability, *kernel_ms;
-};
-
-// (the destructor waits for the stream first: on an early return no pending copy outlives a buffer, host or device)
-struct DevBufs {
-    hipStream_t stream;
-    std::vector<void*> ptrs;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    explicit DevBufs(hipStream_t s) : stream(s) {}
-    ~DevBufs() {
-        (void)hipStreamSynchronize(stream);
-        for (void* p : ptrs) (void)hipFree(p);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    }
-    template <typename T>
-    T* get(size_t n) {
-        void* p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return nullptr;
-        ptrs.push_back(p);
-        return (T*)p;
-    }
 };
 
 int check_stab_out(const StabOut& o) {
@@ -275,14 +361,11 @@ int run_stability(hipStream_t stream, const std::vector<StabGroup>& groups, cons
     HIPCK(hipMemcpyAsync(dgroups, groups.data(), G * sizeof(StabGroup), hipMemcpyHostToDevice, stream));
     HIPCK(hipMemcpyAsync(dsrc, src.data(), T * sizeof(double*), hipMemcpyHostToDevice, stream));
     HIPCK(hipMemcpyAsync(derr, err.data(), T * sizeof(double), hipMemcpyHostToDevice, stream));
-    if (o.kernel_ms) {
-        HIPCK(hipEventCreate(&d.e0));
-        HIPCK(hipEventCreate(&d.e1));
-        HIPCK(hipEventRecord(d.e0, stream));
-    }
+    const hipEvent_t e0 = o.kernel_ms ? d.mark() : nullptr;
     launch_stability(a, (int)G, stream);
     HIPCK(hipGetLastError());
-    if (o.kernel_ms) HIPCK(hipEventRecord(d.e1, stream));
+    const hipEvent_t e1 = o.kernel_ms ? d.mark() : nullptr;
+    if (o.kernel_ms && (!e0 || !e1)) return fail("event record failed");
     HIPCK(hipMemcpyAsync(o.assignments, a.assign, T * STAB_K * sizeof(int), hipMemcpyDeviceToHost, stream));
     HIPCK(hipMemcpyAsync(abz.data(), a.a, abz.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
     HIPCK(hipMemcpyAsync(o.consensus, a.consensus, G * STAB_K * VMAX * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -300,7 +383,7 @@ int run_stability(hipStream_t stream, const std::vector<StabGroup>& groups, cons
     }
     if (o.kernel_ms) {
         float ms = 0.f;
-        HIPCK(hipEventElapsedTime(&ms, d.e0, d.e1));
+        HIPCK(hipEventElapsedTime(&ms, e0, e1));
         *o.kernel_ms = (double)ms;
     }
     return 0;
@@ -321,13 +404,8 @@ int salnmf_batch_create(int device, int n_features, int64_t n_samples, int n_mem
     if (n_members < 1 || !n_signatures) return fail("a batch needs at least one member");
     for (int m = 0; m < n_members; ++m)
         if (n_signatures[m] < 1 || n_signatures[m] > 16) return fail("member %d: n_signatures must be in [1, 16], got %d", m, n_signatures[m]);
-    int ndev = 0;
-    HIPCK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail("device %d out of range (%d visible)", device, ndev);
-    HIPCK(hipSetDevice(device));
     hipDeviceProp_t prop;
-    HIPCK(hipGetDeviceProperties(&prop, device));
-    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0) return fail("this build targets gfx950 only; device %d is %s", device, prop.gcnArchName);
+    CK(open_device(device, &prop));
 
     salnmf_batch* b = new salnmf_batch();
     b->device = device;
@@ -522,33 +600,9 @@ int salnmf_batch_resample(salnmf_batch* b, int n_resamples, uint64_t seed) {
     if (!b->x_ok) return fail("upload X first");
     CK(check_resample_args(n_resamples));
     if (b->F) return fail("this batch holds %d count splits: resamples and splits exclude each other on one batch (upload X again to drop them)", b->F);
-    std::vector<uint32_t> counts;
-    CK(check_counts(b->hostX.data(), b->N, b->V, counts));
-    HIPCK(hipSetDevice(b->device));
-    HIPCK(hipStreamSynchronize(b->stream));
-    drop_resamples(b);
-    uint32_t* dcounts = nullptr;
-    auto cleanup = [&](int rc) {
-        if (dcounts) (void)hipFree(dcounts);
-        if (rc) drop_resamples(b);
-        return rc;
-    };
-    const size_t xsz = (size_t)b->Np * VMAX, csz = (size_t)b->Np * 16;
-    if (hipMalloc(&b->Xr, (size_t)n_resamples * xsz * sizeof(double)) != hipSuccess || hipMalloc(&b->xlxr, (size_t)n_resamples * csz * sizeof(double)) != hipSuccess ||
-        hipMalloc(&dcounts, counts.size() * sizeof(uint32_t)) != hipSuccess)
-        return cleanup(fail("hipMalloc failed (%d resamples)", n_resamples));
+    CK(draw_into_slots(b, n_resamples, batch_resample_launch(b, n_resamples, seed)));
     b->R = n_resamples;
-    if (hipMemcpyAsync(dcounts, counts.data(), counts.size() * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream) != hipSuccess)
-        return cleanup(fail("hipMemcpy failed"));
-    // straight into the slots, in X's layout: pad rows and columns 0, the N x V block clipped as upload_X(clip = 1) clips
-    launch_resample(ResampleArgs{dcounts, b->Xr, b->N, b->Np, b->V, VMAX, (uint32_t)seed, (uint32_t)(seed >> 32), SALNMF_EPSILON}, n_resamples, b->stream);
-    if (hipGetLastError() != hipSuccess) return cleanup(fail("resample launch failed"));
-    for (int r = 0; r < n_resamples; ++r) {
-        launch_xlogx_lane(b->Xr + (size_t)r * xsz, b->Np, b->V, b->xlxr + (size_t)r * csz, b->stream);
-        if (hipGetLastError() != hipSuccess) return cleanup(fail("xlogx launch failed"));
-    }
-    if (hipStreamSynchronize(b->stream) != hipSuccess) return cleanup(fail("resample failed on the device"));
-    return cleanup(0);
+    return 0;
 }
 
 int salnmf_batch_split(salnmf_batch* b, int n_splits, uint64_t thr, uint64_t seed) {
@@ -556,36 +610,10 @@ int salnmf_batch_split(salnmf_batch* b, int n_splits, uint64_t thr, uint64_t see
     if (!b->x_ok) return fail("upload X first");
     CK(check_split_args(n_splits, thr));
     if (b->R && !b->F) return fail("this batch holds %d resamples: resamples and splits exclude each other on one batch (upload X again to drop them)", b->R);
-    std::vector<uint32_t> counts;
-    CK(check_counts(b->hostX.data(), b->N, b->V, counts));
-    HIPCK(hipSetDevice(b->device));
-    HIPCK(hipStreamSynchronize(b->stream));
-    drop_resamples(b);
-    uint32_t* dcounts = nullptr;
-    auto cleanup = [&](int rc) {
-        if (dcounts) (void)hipFree(dcounts);
-        if (rc) drop_resamples(b);
-        return rc;
-    };
-    const size_t xsz = (size_t)b->Np * VMAX, csz = (size_t)b->Np * 16;
-    const int slots = 2 * n_splits;
-    if (hipMalloc(&b->Xr, (size_t)slots * xsz * sizeof(double)) != hipSuccess || hipMalloc(&b->xlxr, (size_t)slots * csz * sizeof(double)) != hipSuccess ||
-        hipMalloc(&dcounts, counts.size() * sizeof(uint32_t)) != hipSuccess)
-        return cleanup(fail("hipMalloc failed (%d splits)", n_splits));
-    b->R = slots;
+    CK(draw_into_slots(b, 2 * n_splits, batch_split_launch(b, n_splits, thr, seed)));
+    b->R = 2 * n_splits;
     b->F = n_splits;
-    if (hipMemcpyAsync(dcounts, counts.data(), counts.size() * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream) != hipSuccess)
-        return cleanup(fail("hipMemcpy failed"));
-    // straight into the slots, in X's layout: train split f is slot f, test split f slot F + f
-    launch_split(SplitArgs{dcounts, b->Xr, b->Xr + (size_t)n_splits * xsz, b->N, b->Np, b->V, VMAX, (uint32_t)seed, (uint32_t)(seed >> 32), thr, SALNMF_EPSILON},
-                 n_splits, b->stream);
-    if (hipGetLastError() != hipSuccess) return cleanup(fail("split launch failed"));
-    for (int s = 0; s < slots; ++s) {
-        launch_xlogx_lane(b->Xr + (size_t)s * xsz, b->Np, b->V, b->xlxr + (size_t)s * csz, b->stream);
-        if (hipGetLastError() != hipSuccess) return cleanup(fail("xlogx launch failed"));
-    }
-    if (hipStreamSynchronize(b->stream) != hipSuccess) return cleanup(fail("split failed on the device"));
-    return cleanup(0);
+    return 0;
 }
 
 int salnmf_batch_heldout_kl(salnmf_batch* b, int n_members, const int* members, const int* datasets, double scale, double* out) {
@@ -598,9 +626,8 @@ int salnmf_batch_heldout_kl(salnmf_batch* b, int n_members, const int* members, 
     // (host buffers of the asynchronous copies: declared before d, so they outlive its wait for the stream)
     std::vector<const double*> xs((size_t)n_members);
     for (int i = 0; i < n_members; ++i) {
-        if (datasets[i] < -1 || datasets[i] >= b->R)
-            return fail("dataset %d out of range (%d resamples or split halves; -1 is the uploaded X)", datasets[i], b->R);
-        xs[(size_t)i] = datasets[i] < 0 ? b->X : b->Xr + (size_t)datasets[i] * b->Np * VMAX;
+        CK(check_dataset(b, datasets[i]));
+        xs[(size_t)i] = dataset_ptr(b, datasets[i]);
     }
     const std::vector<double> hs(16, scale);
     std::vector<double> host((size_t)b->M * b->Np);
@@ -627,7 +654,7 @@ int salnmf_batch_heldout_kl(salnmf_batch* b, int n_members, const int* members, 
 
 int salnmf_batch_set_dataset(salnmf_batch* b, int member, int dataset) {
     CK(check_member(b, member));
-    if (dataset < -1 || dataset >= b->R) return fail("dataset %d out of range (%d resamples or split halves; -1 is the uploaded X)", dataset, b->R);
+    CK(check_dataset(b, dataset));
     if (b->dataset[(size_t)member] != dataset) point_member(b, member, dataset);
     return 0;
 }
@@ -635,9 +662,9 @@ int salnmf_batch_set_dataset(salnmf_batch* b, int member, int dataset) {
 int salnmf_batch_download_dataset(salnmf_batch* b, int dataset, int raw, double* out) {
     if (!b || !out) return fail("null argument");
     if (!b->x_ok) return fail("upload X first");
-    if (dataset < -1 || dataset >= b->R) return fail("dataset %d out of range (%d resamples or split halves; -1 is the uploaded X)", dataset, b->R);
+    CK(check_dataset(b, dataset));
     HIPCK(hipSetDevice(b->device));
-    const double* src = dataset < 0 ? b->X : b->Xr + (size_t)dataset * b->Np * VMAX;
+    const double* src = dataset_ptr(b, dataset);
     if (raw) {
         HIPCK(hipMemcpyAsync(out, src, (size_t)b->Np * VMAX * sizeof(double), hipMemcpyDeviceToHost, b->stream));
         HIPCK(hipStreamSynchronize(b->stream));
@@ -656,126 +683,28 @@ int salnmf_batch_download_dataset(salnmf_batch* b, int dataset, int raw, double*
 
 int salnmf_resample_counts(int device, const double* X, int64_t n_samples, int n_features, int n_resamples, uint64_t seed, double* out) {
     if (!X || !out) return fail("null argument");
-    if (n_samples < 1 || n_samples > 0x7fffffff) return fail("n_samples must be in [1, 2^31), got %lld", (long long)n_samples);
-    if (n_features < 1 || n_features > RESAMPLE_VMAX) return fail("n_features must be in [1, %d], got %d", RESAMPLE_VMAX, n_features);
     CK(check_resample_args(n_resamples));
-    std::vector<uint32_t> counts;
-    CK(check_counts(X, n_samples, n_features, counts));
-    int ndev = 0;
-    HIPCK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail("device %d out of range (%d visible)", device, ndev);
-    HIPCK(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    HIPCK(hipGetDeviceProperties(&prop, device));
-    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0) return fail("this build targets gfx950 only; device %d is %s", device, prop.gcnArchName);
-    uint32_t* dcounts = nullptr;
-    double* dout = nullptr;
-    auto cleanup = [&](int rc) {
-        if (dcounts) (void)hipFree(dcounts);
-        if (dout) (void)hipFree(dout);
-        return rc;
-    };
-    const size_t nout = (size_t)n_resamples * counts.size();
-    if (hipMalloc(&dcounts, counts.size() * sizeof(uint32_t)) != hipSuccess || hipMalloc(&dout, nout * sizeof(double)) != hipSuccess)
-        return cleanup(fail("hipMalloc failed (%d resamples of %lld x %d)", n_resamples, (long long)n_samples, n_features));
-    if (hipMemcpy(dcounts, counts.data(), counts.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return cleanup(fail("hipMemcpy failed"));
-    launch_resample(ResampleArgs{dcounts, dout, n_samples, n_samples, n_features, n_features, (uint32_t)seed, (uint32_t)(seed >> 32), 0.0}, n_resamples, nullptr);
-    if (hipGetLastError() != hipSuccess) return cleanup(fail("resample launch failed"));
-    if (hipMemcpy(out, dout, nout * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return cleanup(fail("resample failed on the device"));
-    return cleanup(0);
+    return draw_stand_alone(device, X, n_samples, n_features, n_resamples, out, nullptr, [=](const uint32_t* dcounts, double* dout) {
+        launch_resample(ResampleArgs{dcounts, dout, n_samples, n_samples, n_features, n_features, (uint32_t)seed, (uint32_t)(seed >> 32), 0.0}, n_resamples, nullptr);
+    });
 }
 
 int salnmf_split_counts(int device, const double* X, int64_t n_samples, int n_features, int n_splits, uint64_t thr, uint64_t seed, double* train_out,
                         double* test_out) {
     if (!X || !train_out || !test_out) return fail("null argument");
-    if (n_samples < 1 || n_samples > 0x7fffffff) return fail("n_samples must be in [1, 2^31), got %lld", (long long)n_samples);
-    if (n_features < 1 || n_features > RESAMPLE_VMAX) return fail("n_features must be in [1, %d], got %d", RESAMPLE_VMAX, n_features);
     CK(check_split_args(n_splits, thr));
-    std::vector<uint32_t> counts;
-    CK(check_counts(X, n_samples, n_features, counts));
-    int ndev = 0;
-    HIPCK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail("device %d out of range (%d visible)", device, ndev);
-    HIPCK(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    HIPCK(hipGetDeviceProperties(&prop, device));
-    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0) return fail("this build targets gfx950 only; device %d is %s", device, prop.gcnArchName);
-    uint32_t* dcounts = nullptr;
-    double* dout = nullptr;  // train | test
-    auto cleanup = [&](int rc) {
-        if (dcounts) (void)hipFree(dcounts);
-        if (dout) (void)hipFree(dout);
-        return rc;
-    };
-    const size_t nout = (size_t)n_splits * counts.size();
-    if (hipMalloc(&dcounts, counts.size() * sizeof(uint32_t)) != hipSuccess || hipMalloc(&dout, 2 * nout * sizeof(double)) != hipSuccess)
-        return cleanup(fail("hipMalloc failed (%d splits of %lld x %d)", n_splits, (long long)n_samples, n_features));
-    if (hipMemcpy(dcounts, counts.data(), counts.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return cleanup(fail("hipMemcpy failed"));
-    launch_split(SplitArgs{dcounts, dout, dout + nout, n_samples, n_samples, n_features, n_features, (uint32_t)seed, (uint32_t)(seed >> 32), thr, 0.0}, n_splits,
-                 nullptr);
-    if (hipGetLastError() != hipSuccess) return cleanup(fail("split launch failed"));
-    if (hipMemcpy(train_out, dout, nout * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(test_out, dout + nout, nout * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-        return cleanup(fail("split failed on the device"));
-    return cleanup(0);
+    return draw_stand_alone(device, X, n_samples, n_features, n_splits, train_out, test_out, [=](const uint32_t* dcounts, double* dout) {
+        double* test = dout + (size_t)n_splits * n_samples * n_features;
+        launch_split(SplitArgs{dcounts, dout, test, n_samples, n_samples, n_features, n_features, (uint32_t)seed, (uint32_t)(seed >> 32), thr, 0.0}, n_splits, nullptr);
+    });
 }
 
 int salnmf_profile_split(salnmf_batch* b, int n_splits, uint64_t thr, uint64_t seed, int n_calls, double* avg_ms) {
-    if (!b || !avg_ms) return fail("null argument");
-    if (!b->x_ok) return fail("upload X first");
-    if (n_calls < 1) return fail("n_calls must be positive");
-    CK(salnmf_batch_split(b, n_splits, thr, seed));  // (validates, allocates the slots, warms the kernel up)
-    std::vector<uint32_t> counts;
-    CK(check_counts(b->hostX.data(), b->N, b->V, counts));
-    uint32_t* dcounts = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto cleanup = [&](int rc) {
-        if (dcounts) (void)hipFree(dcounts);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        return rc;
-    };
-    if (hipMalloc(&dcounts, counts.size() * sizeof(uint32_t)) != hipSuccess || hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)
-        return cleanup(fail("hipMalloc failed"));
-    if (hipMemcpy(dcounts, counts.data(), counts.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return cleanup(fail("hipMemcpy failed"));
-    const SplitArgs a{dcounts, b->Xr, b->Xr + (size_t)n_splits * b->Np * VMAX, b->N, b->Np, b->V, VMAX, (uint32_t)seed, (uint32_t)(seed >> 32), thr, SALNMF_EPSILON};
-    (void)hipEventRecord(e0, b->stream);
-    for (int i = 0; i < n_calls; ++i) launch_split(a, n_splits, b->stream);  // (the same bits every time)
-    (void)hipEventRecord(e1, b->stream);
-    if (hipGetLastError() != hipSuccess || hipEventSynchronize(e1) != hipSuccess) return cleanup(fail("split failed on the device"));
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    *avg_ms = (double)ms / n_calls;
-    return cleanup(0);
+    return profile_draw(b, n_calls, avg_ms, [=] { return salnmf_batch_split(b, n_splits, thr, seed); }, batch_split_launch(b, n_splits, thr, seed));
 }
 
 int salnmf_profile_resample(salnmf_batch* b, int n_resamples, uint64_t seed, int n_calls, double* avg_ms) {
-    if (!b || !avg_ms) return fail("null argument");
-    if (!b->x_ok) return fail("upload X first");
-    if (n_calls < 1) return fail("n_calls must be positive");
-    CK(salnmf_batch_resample(b, n_resamples, seed));  // (validates, allocates the slots, warms the kernel up)
-    std::vector<uint32_t> counts;
-    CK(check_counts(b->hostX.data(), b->N, b->V, counts));
-    uint32_t* dcounts = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto cleanup = [&](int rc) {
-        if (dcounts) (void)hipFree(dcounts);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        return rc;
-    };
-    if (hipMalloc(&dcounts, counts.size() * sizeof(uint32_t)) != hipSuccess || hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)
-        return cleanup(fail("hipMalloc failed"));
-    if (hipMemcpy(dcounts, counts.data(), counts.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return cleanup(fail("hipMemcpy failed"));
-    const ResampleArgs a{dcounts, b->Xr, b->N, b->Np, b->V, VMAX, (uint32_t)seed, (uint32_t)(seed >> 32), SALNMF_EPSILON};
-    (void)hipEventRecord(e0, b->stream);
-    for (int i = 0; i < n_calls; ++i) launch_resample(a, n_resamples, b->stream);  // (the same bits every time)
-    (void)hipEventRecord(e1, b->stream);
-    if (hipGetLastError() != hipSuccess || hipEventSynchronize(e1) != hipSuccess) return cleanup(fail("resample failed on the device"));
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    *avg_ms = (double)ms / n_calls;
-    return cleanup(0);
+    return profile_draw(b, n_calls, avg_ms, [=] { return salnmf_batch_resample(b, n_resamples, seed); }, batch_resample_launch(b, n_resamples, seed));
 }
 
 int salnmf_batch_stability(salnmf_batch* b, int n_groups, const int* group_offsets, const int* members, const double* errors, int max_rounds,
@@ -830,25 +759,16 @@ int salnmf_signature_stability(int device, const double* signatures, int n_group
         groups.push_back(StabGroup{n_signatures[g], n_members[g], (int)T});
         T += (size_t)n_members[g];
     }
-    int ndev = 0;
-    HIPCK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail("device %d out of range (%d visible)", device, ndev);
-    HIPCK(hipSetDevice(device));
     hipDeviceProp_t prop;
-    HIPCK(hipGetDeviceProperties(&prop, device));
-    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0) return fail("this build targets gfx950 only; device %d is %s", device, prop.gcnArchName);
-    double* dsig = nullptr;
+    CK(open_device(device, &prop));
+    DevBufs d;
     const size_t n = T * STAB_K * VMAX;
-    if (hipMalloc(&dsig, n * sizeof(double)) != hipSuccess) return fail("hipMalloc failed (%zu signature matrices)", T);
-    int rc = 0;
-    if (hipMemcpy(dsig, signatures, n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = fail("hipMemcpy failed");
-    if (!rc) {
-        std::vector<const double*> src(T);
-        for (size_t t = 0; t < T; ++t) src[t] = dsig + t * STAB_K * VMAX;
-        rc = run_stability(nullptr, groups, src, VMAX, n_features, errors, max_rounds, o);
-    }
-    (void)hipFree(dsig);
-    return rc;
+    double* dsig = d.get<double>(n);
+    if (!dsig) return fail("hipMalloc failed (%zu signature matrices)", T);
+    HIPCK(hipMemcpy(dsig, signatures, n * sizeof(double), hipMemcpyHostToDevice));
+    std::vector<const double*> src(T);
+    for (size_t t = 0; t < T; ++t) src[t] = dsig + t * STAB_K * VMAX;
+    return run_stability(nullptr, groups, src, VMAX, n_features, errors, max_rounds, o);
 }
 
 }  // extern "C"

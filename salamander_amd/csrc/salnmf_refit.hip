@@ -5,45 +5,17 @@
 #define SALNMF_REFIT_KERNELS 1
 #include "../../include/salnmf.h"
 #include "salnmf_kernels.h"
-#include "salnmf_error.h"
+#include "salnmf_device.h"
 #include "salnmf_refit.h"
 #include "salnmf_assign.h"
 
 #include <algorithm>
 #include <cmath>
-#include <string>
 #include <vector>
 
 using namespace salnmf;
 
 namespace {
-
-// (the destructor waits for the stream first: on an early return no pending copy outlives a buffer, host or device)
-struct RefitBufs {
-    hipStream_t stream = nullptr;
-    std::vector<void*> ptrs;
-    std::vector<hipEvent_t> events;
-    ~RefitBufs() {
-        if (stream) (void)hipStreamSynchronize(stream);
-        for (void* p : ptrs) (void)hipFree(p);
-        for (hipEvent_t e : events) (void)hipEventDestroy(e);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-    template <typename T>
-    T* get(size_t n) {
-        void* p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return nullptr;
-        ptrs.push_back(p);
-        return (T*)p;
-    }
-    // an event recorded on the stream now, or null
-    hipEvent_t mark() {
-        hipEvent_t e = nullptr;
-        if (hipEventCreate(&e) != hipSuccess) return nullptr;
-        events.push_back(e);
-        return hipEventRecord(e, stream) == hipSuccess ? e : nullptr;
-    }
-};
 
 // What both entry points check and prepare before any launch: the ranges, the signatures, the counts clipped to EPSILON
 // (and as integers for the resampler when R > 0), the quantiles' indices, the device and its CU count.
@@ -91,13 +63,8 @@ int refit_prepare(int device, const double* counts, int64_t N, int V, const doub
             in.red.index[i] = std::min(R - 1, std::max(0, (int)(qv <= 0.5 ? std::floor(pos) : std::ceil(pos))));
         }
     }
-    int ndev = 0;
-    HIPCK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail("device %d out of range (%d visible)", device, ndev);
-    HIPCK(hipSetDevice(device));
     hipDeviceProp_t prop;
-    HIPCK(hipGetDeviceProperties(&prop, device));
-    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0) return fail("this build targets gfx950 only; device %d is %s", device, prop.gcnArchName);
+    CK(open_device(device, &prop));
     in.cus = prop.multiProcessorCount;
     return 0;
 }
@@ -160,8 +127,8 @@ extern "C" int salnmf_refit_exposures(int device, const double* counts, int64_t 
     const int chunk = R > 0 ? (int)std::max<int64_t>(1, std::min<int64_t>(R, budget / (int64_t)(sizeof(double) * (size_t)N * V))) : 0;
 
     // (host buffers of the asynchronous copies live until d's destructor has waited for the stream)
-    RefitBufs d;
-    HIPCK(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
+    DevBufs d;
+    CK(d.own_stream());
     const size_t NR = (size_t)N * (size_t)std::max(R, 1);
     double* dW = d.get<double>((size_t)K * V);
     double* dX = d.get<double>((size_t)N * V);
@@ -283,8 +250,8 @@ extern "C" int salnmf_assign_signatures(int device, const double* counts, int64_
     const int64_t budget = chunk_bytes > 0 ? chunk_bytes : (int64_t)256 << 20;
     const int chunk = R > 0 ? (int)std::max<int64_t>(1, std::min<int64_t>(R, budget / (int64_t)(sizeof(double) * (size_t)N * V))) : 0;
 
-    RefitBufs d;
-    HIPCK(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
+    DevBufs d;
+    CK(d.own_stream());
     const size_t NK = (size_t)N * K, NR = (size_t)N * (size_t)std::max(R, 1);
     double* dW = d.get<double>((size_t)K * V);
     double* dX = d.get<double>((size_t)N * V);

@@ -44,11 +44,9 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
     o[0] = c0, o[1] = c1, o[2] = c2, o[3] = c3;
 }
 
-// the bin of one draw: t = high 64 bits of u * T (T < 2^32, so t < T fits 32 bits), then the smallest v with cum[v] > t
-__device__ __forceinline__ int resample_bin(uint32_t ulo, uint32_t uhi, uint32_t T, const uint32_t* cum, int V) {
-    const uint64_t low = (uint64_t)ulo * T;
-    const uint32_t t = (uint32_t)(((uint64_t)uhi * T + (low >> 32)) >> 32);
-    int lo = 0, hi = V - 1;  // cum[V - 1] = T > t: the answer is in [0, V - 1]
+// the cell of position t < cum[V - 1]: the smallest v with cum[v] > t
+__device__ __forceinline__ int upper_cell(uint32_t t, const uint32_t* cum, int V) {
+    int lo = 0, hi = V - 1;  // cum[V - 1] > t: the answer is in [0, V - 1]
     while (lo < hi) {
         const int mid = (lo + hi) >> 1;
         if (cum[mid] > t)
@@ -59,21 +57,28 @@ __device__ __forceinline__ int resample_bin(uint32_t ulo, uint32_t uhi, uint32_t
     return lo;
 }
 
-// One workgroup per (output row, resample): blockIdx.x = row, blockIdx.y = resample.
-__global__ void __launch_bounds__(RESAMPLE_BLOCK) resample_counts_kernel(ResampleArgs a) {
+__device__ __forceinline__ double clipped_count(uint32_t c, double floor) { return (double)c < floor ? floor : (double)c; }
+
+// One row of one draw, by one workgroup of RESAMPLE_BLOCK lanes: everything the count-drawing kernels share.  Row n of
+// `counts` ([N][V]) is loaded, its T_n trials are drawn two per Philox block, and the row is written out `ld` cells wide
+// (ld >= V; a row n >= N is a pad row of the batch layout).  What tells one kind of draw from another is `Draw`, passed by value:
+//   stream, index   the second and the fourth counter word of every block (the first is q, the third n);
+//   place(j, ulo, uhi, T, cum, V)   the cell that trial j, with the 64-bit draw u = ulo | uhi << 32, adds one to, or -1 for none;
+//   write_row(tid, ld, V, floor, x, hist)   the row from its counts x and the histogram of the placed trials: cells below V
+//                   clipped to `floor`, cells from V on zero (a pad row is written with V = 0 and reads neither array).
+template <typename Draw>
+__device__ __forceinline__ void count_draw_row(const uint32_t* __restrict__ counts, int64_t N, int V, int ld, uint32_t key0, uint32_t key1, double floor,
+                                               const Draw d) {
     __shared__ uint32_t cum[RESAMPLE_VMAX];
     __shared__ uint32_t hist[RESAMPLE_VMAX];
     __shared__ uint32_t part[RESAMPLE_BLOCK];
     const int tid = threadIdx.x;
     const int64_t n = blockIdx.x;
-    const uint32_t r = blockIdx.y + a.first;
-    double* out = a.out + ((size_t)blockIdx.y * a.rows_out + n) * a.ld;
-    if (n >= a.N) {  // a pad row of the batch layout
-        for (int v = tid; v < a.ld; v += RESAMPLE_BLOCK) out[v] = 0.0;
+    if (n >= N) {  // a pad row of the batch layout
+        d.write_row(tid, ld, 0, floor, nullptr, nullptr);
         return;
     }
-    const int V = a.V;
-    const uint32_t* x = a.counts + (size_t)n * V;
+    const uint32_t* x = counts + (size_t)n * V;
     for (int v = tid; v < V; v += RESAMPLE_BLOCK) {
         cum[v] = x[v];
         hist[v] = 0;
@@ -82,13 +87,13 @@ __global__ void __launch_bounds__(RESAMPLE_BLOCK) resample_counts_kernel(Resampl
     // inclusive prefix sums: every lane scans its own stretch of `chunk` entries, the stretches' totals are scanned across
     // the workgroup, and every lane adds the total of the stretches before its own
     const int chunk = (V + RESAMPLE_BLOCK - 1) / RESAMPLE_BLOCK;
-    const int first = tid * chunk, last = min(first + chunk, V);
+    const int first = min(tid * chunk, V), last = min(first + chunk, V);
     uint32_t sum = 0;
     for (int v = first; v < last; ++v) cum[v] = sum += cum[v];
     part[tid] = sum;
     __syncthreads();
-    for (int d = 1; d < RESAMPLE_BLOCK; d <<= 1) {
-        const uint32_t add = tid >= d ? part[tid - d] : 0;
+    for (int s = 1; s < RESAMPLE_BLOCK; s <<= 1) {
+        const uint32_t add = tid >= s ? part[tid - s] : 0;
         __syncthreads();
         part[tid] += add;
         __syncthreads();
@@ -101,19 +106,37 @@ __global__ void __launch_bounds__(RESAMPLE_BLOCK) resample_counts_kernel(Resampl
     const uint32_t nblocks = (T >> 1) + (T & 1);
     for (uint32_t q = tid; q < nblocks; q += RESAMPLE_BLOCK) {
         uint32_t o[4];
-        philox4x32_10(q, 0u, (uint32_t)n, r, a.key0, a.key1, o);
-        atomicAdd(&hist[resample_bin(o[0], o[1], T, cum, V)], 1u);
-        if (2 * (uint64_t)q + 1 < T) atomicAdd(&hist[resample_bin(o[2], o[3], T, cum, V)], 1u);
+        philox4x32_10(q, d.stream, (uint32_t)n, d.index, key0, key1, o);
+        const uint32_t j = 2u * q;  // (j + 1 <= T - 1 < 2^32 where it is used)
+        int cell = d.place(j, o[0], o[1], T, cum, V);
+        if (cell >= 0) atomicAdd(&hist[cell], 1u);
+        if (2 * (uint64_t)q + 1 < T) {
+            cell = d.place(j + 1u, o[2], o[3], T, cum, V);
+            if (cell >= 0) atomicAdd(&hist[cell], 1u);
+        }
     }
     __syncthreads();
-    for (int v = tid; v < a.ld; v += RESAMPLE_BLOCK) {
-        double c = 0.0;
-        if (v < V) {
-            c = (double)hist[v];
-            c = c < a.floor ? a.floor : c;
-        }
-        out[v] = c;
+    d.write_row(tid, ld, V, floor, x, hist);
+}
+
+// the resampler's draw: trial j lands at position t = high 64 bits of u * T (T < 2^32, so t < T fits 32 bits)
+struct ResampleDraw {
+    static constexpr uint32_t stream = 0u;
+    uint32_t index;  // the resample
+    double* out;     // its row
+    __device__ int place(uint32_t, uint32_t ulo, uint32_t uhi, uint32_t T, const uint32_t* cum, int V) const {
+        const uint64_t low = (uint64_t)ulo * T;
+        return upper_cell((uint32_t)(((uint64_t)uhi * T + (low >> 32)) >> 32), cum, V);
     }
+    __device__ void write_row(int tid, int ld, int V, double floor, const uint32_t*, const uint32_t* hist) const {
+        for (int v = tid; v < ld; v += RESAMPLE_BLOCK) out[v] = v < V ? clipped_count(hist[v], floor) : 0.0;
+    }
+};
+
+// One workgroup per (output row, resample): blockIdx.x = row, blockIdx.y = resample.
+__global__ void __launch_bounds__(RESAMPLE_BLOCK) resample_counts_kernel(ResampleArgs a) {
+    const ResampleDraw d{blockIdx.y + a.first, a.out + ((size_t)blockIdx.y * a.rows_out + blockIdx.x) * a.ld};
+    count_draw_row(a.counts, a.N, a.V, a.ld, a.key0, a.key1, a.floor, d);
 }
 
 inline void launch_resample(const ResampleArgs& a, int n_resamples, hipStream_t stream) {

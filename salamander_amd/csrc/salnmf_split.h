@@ -31,82 +31,34 @@ struct SplitArgs {
     double floor;                         // entries of the N x V blocks are max(count, floor): 0 (raw) or SALNMF_EPSILON
 };
 
-// the cell of mutation j < cum[V - 1]: the smallest v with cum[v] > j
-__device__ __forceinline__ int split_cell(uint32_t j, const uint32_t* cum, int V) {
-    int lo = 0, hi = V - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (cum[mid] > j)
-            hi = mid;
-        else
-            lo = mid + 1;
+// the split's draw: mutation j stays in its own cell, and is counted (sent to train) iff its draw is below thr
+struct SplitDraw {
+    static constexpr uint32_t stream = SPLIT_STREAM;
+    uint32_t index;  // the split
+    uint64_t thr;
+    double *train, *test;  // its rows
+    __device__ int place(uint32_t j, uint32_t ulo, uint32_t uhi, uint32_t, const uint32_t* cum, int V) const {
+        return ((uint64_t)uhi << 32 | ulo) < thr ? upper_cell(j, cum, V) : -1;
     }
-    return lo;
-}
-
-// One workgroup per (output row, split): blockIdx.x = row, blockIdx.y = split.  LDS as resample_counts_kernel: the prefix
-// sums and one histogram (train); test is x - train at write-out.
-__global__ void __launch_bounds__(RESAMPLE_BLOCK) split_counts_kernel(SplitArgs a) {
-    __shared__ uint32_t cum[RESAMPLE_VMAX];
-    __shared__ uint32_t hist[RESAMPLE_VMAX];
-    __shared__ uint32_t part[RESAMPLE_BLOCK];
-    const int tid = threadIdx.x;
-    const int64_t n = blockIdx.x;
-    const uint32_t f = blockIdx.y;
-    const size_t row = ((size_t)f * a.rows_out + n) * a.ld;
-    double* train = a.train + row;
-    double* test = a.test + row;
-    if (n >= a.N) {  // a pad row of the batch layout
-        for (int v = tid; v < a.ld; v += RESAMPLE_BLOCK) train[v] = test[v] = 0.0;
-        return;
-    }
-    const int V = a.V;
-    const uint32_t* x = a.counts + (size_t)n * V;
-    for (int v = tid; v < V; v += RESAMPLE_BLOCK) {
-        cum[v] = x[v];
-        hist[v] = 0;
-    }
-    __syncthreads();
-    // inclusive prefix sums, as the resampler builds them: every lane scans its own stretch, the stretches' totals are
-    // scanned across the workgroup, and every lane adds the total of the stretches before its own
-    const int chunk = (V + RESAMPLE_BLOCK - 1) / RESAMPLE_BLOCK;
-    const int first = min(tid * chunk, V), last = min(first + chunk, V);
-    uint32_t sum = 0;
-    for (int v = first; v < last; ++v) cum[v] = sum += cum[v];
-    part[tid] = sum;
-    __syncthreads();
-    for (int d = 1; d < RESAMPLE_BLOCK; d <<= 1) {
-        const uint32_t add = tid >= d ? part[tid - d] : 0;
-        __syncthreads();
-        part[tid] += add;
-        __syncthreads();
-    }
-    const uint32_t before = tid ? part[tid - 1] : 0;
-    for (int v = first; v < last; ++v) cum[v] += before;
-    __syncthreads();
-    const uint32_t T = cum[V - 1];
-    // T draws, two per Philox block; lanes stride over the blocks (T < 2^32: the block index fits 32 bits)
-    const uint32_t nblocks = (T >> 1) + (T & 1);
-    for (uint32_t q = tid; q < nblocks; q += RESAMPLE_BLOCK) {
-        uint32_t o[4];
-        philox4x32_10(q, SPLIT_STREAM, (uint32_t)n, f, a.key0, a.key1, o);
-        const uint32_t j = 2u * q;  // (j + 1 <= T - 1 < 2^32 where it is used)
-        if (((uint64_t)o[1] << 32 | o[0]) < a.thr) atomicAdd(&hist[split_cell(j, cum, V)], 1u);
-        if (2 * (uint64_t)q + 1 < T && ((uint64_t)o[3] << 32 | o[2]) < a.thr) atomicAdd(&hist[split_cell(j + 1u, cum, V)], 1u);
-    }
-    __syncthreads();
-    for (int v = tid; v < a.ld; v += RESAMPLE_BLOCK) {
-        double tr = 0.0, te = 0.0;
-        if (v < V) {
-            const uint32_t h = hist[v];
-            tr = (double)h;
-            te = (double)(x[v] - h);
-            tr = tr < a.floor ? a.floor : tr;
-            te = te < a.floor ? a.floor : te;
+    __device__ void write_row(int tid, int ld, int V, double floor, const uint32_t* x, const uint32_t* hist) const {
+        for (int v = tid; v < ld; v += RESAMPLE_BLOCK) {
+            double tr = 0.0, te = 0.0;
+            if (v < V) {
+                tr = clipped_count(hist[v], floor);
+                te = clipped_count(x[v] - hist[v], floor);
+            }
+            train[v] = tr;
+            test[v] = te;
         }
-        train[v] = tr;
-        test[v] = te;
     }
+};
+
+// One workgroup per (output row, split): blockIdx.x = row, blockIdx.y = split.  The histogram of count_draw_row is train;
+// test is x - train at write-out.
+__global__ void __launch_bounds__(RESAMPLE_BLOCK) split_counts_kernel(SplitArgs a) {
+    const size_t row = ((size_t)blockIdx.y * a.rows_out + blockIdx.x) * a.ld;
+    const SplitDraw d{blockIdx.y, a.thr, a.train + row, a.test + row};
+    count_draw_row(a.counts, a.N, a.V, a.ld, a.key0, a.key1, a.floor, d);
 }
 
 inline void launch_split(const SplitArgs& a, int n_splits, hipStream_t stream) {

@@ -262,6 +262,32 @@ class KLNMFSweep:
         bound = self.heldout_mean_[best] + self.heldout_sem_[best]
         return min(k for k, mean in zip(self.ns_signatures, self.heldout_mean_) if mean <= bound)
 
+    # ------------------------------------------------------------------ resamples and splits
+    def _draw_datasets(self, batch, counts, slot_of, members) -> float:
+        """The R resamples or the F splits, once: drawn into the batch's own slots (resample r is its dataset r; train split
+        f its dataset f, test split f its dataset F + f) with every batched member pointed at its own, or stand-alone when
+        there is no batch.  Sets ``resamples_``, or ``train_splits_`` and ``test_splits_``; returns the seconds it took."""
+        ta = time.perf_counter()
+        R, F = self.n_resamples, self.n_splits
+        n = R or F
+        if batch is not None:
+            if R:
+                batch.resample(R, self.resample_seed)
+            else:
+                batch.split(F, self.train_fraction, self.split_seed)
+            drawn = [np.stack([batch.download_dataset(first + d) for d in range(n)]) for first in ([0] if R else [0, F])]
+            for i, j in slot_of.items():
+                batch.set_dataset(j, members[i][2])
+        elif R:
+            drawn = [resample_counts(counts, R, self.resample_seed, device=self.device)]
+        else:
+            drawn = split_counts(counts, F, self.train_fraction, self.split_seed, device=self.device)
+        if R:
+            self.resamples_ = drawn[0]
+        else:
+            self.train_splits_, self.test_splits_ = drawn
+        return time.perf_counter() - ta
+
     # ------------------------------------------------------------------ fit
     def fit(self, adata, given_parameters: dict[str, Any] | None = None, init_kwargs: dict[str, Any] | None = None,
             fitting_kwargs: dict[str, Any] | None = None, history: bool = True) -> list[KLNMF]:
@@ -288,35 +314,14 @@ class KLNMFSweep:
                 batch = None  # (a device without the batched kernel: every member takes KLNMF.fit)
         slot_of = {i: j for j, i in enumerate(batch_ids)} if batch is not None else {}
         models: list[KLNMF] = []
-        t_init = t_fallback = t_resample = t_stability = t_split = t_heldout = 0.0
+        t_init = t_fallback = t_draw = t_stability = t_heldout = 0.0
         self.resamples_ = self.train_splits_ = self.test_splits_ = None
         self._clear_stability()
         try:
             if batch is not None:
                 batch.upload_X(np.asarray(adata.X, dtype=np.float64), clip=True)
-            if R:
-                # the R matrices, once: drawn into the batch's own slots, or stand-alone when there is no batch
-                ta = time.perf_counter()
-                if batch is not None:
-                    batch.resample(R, self.resample_seed)
-                    self.resamples_ = np.stack([batch.download_dataset(r) for r in range(R)])
-                    for i, j in slot_of.items():
-                        batch.set_dataset(j, members[i][2])
-                else:
-                    self.resamples_ = resample_counts(counts, R, self.resample_seed, device=self.device)
-                t_resample = time.perf_counter() - ta
-            if F:
-                # the F splits, once: train split f is the batch's dataset f, test split f its dataset F + f
-                ta = time.perf_counter()
-                if batch is not None:
-                    batch.split(F, self.train_fraction, self.split_seed)
-                    self.train_splits_ = np.stack([batch.download_dataset(f) for f in range(F)])
-                    self.test_splits_ = np.stack([batch.download_dataset(F + f) for f in range(F)])
-                    for i, j in slot_of.items():
-                        batch.set_dataset(j, members[i][2])
-                else:
-                    self.train_splits_, self.test_splits_ = split_counts(counts, F, self.train_fraction, self.split_seed, device=self.device)
-                t_split = time.perf_counter() - ta
+            if R or F:
+                t_draw = self._draw_datasets(batch, counts, slot_of, members)
             # every member in order: initialised (batched) or fitted (fallback) exactly as the tutorial's loop would
             # do it, so that the legacy NumPy RNG of the random methods advances the same way
             for i, (k, kwargs, r) in enumerate(members):
@@ -381,11 +386,11 @@ class KLNMFSweep:
         self._fitted = True
         self.member_steps_ = steps
         self.timings_ = {"total_s": time.perf_counter() - t0, "init_s": t_init, "batched_s": t_batched, "fallback_s": t_fallback,
-                         "resample_s": t_resample}
+                         "resample_s": t_draw if R else 0.0}
         if self.stability:
             self.timings_["stability_s"] = t_stability
         if F:
-            self.timings_["split_s"] = t_split
+            self.timings_["split_s"] = t_draw
             self.timings_["heldout_s"] = t_heldout
         return models
 

@@ -17,16 +17,19 @@ MAX_RESAMPLES = 65535
 MAX_FEATURES = 3072
 
 
+def _int_in_range(value, low: int, high: int, message: str) -> int:
+    """``int(value)`` for an integer (no bool) with ``low <= value <= high``, else ``ValueError(message)``."""
+    if not isinstance(value, (int, np.integer)) or isinstance(value, bool) or not low <= int(value) <= high:
+        raise ValueError(message)
+    return int(value)
+
+
 def check_seed(seed) -> int:
-    if not isinstance(seed, (int, np.integer)) or isinstance(seed, bool) or not 0 <= int(seed) < 2**64:
-        raise ValueError("'seed' of a resample must be an integer in [0, 2**64).")
-    return int(seed)
+    return _int_in_range(seed, 0, 2**64 - 1, "'seed' of a resample must be an integer in [0, 2**64).")
 
 
 def check_n_resamples(n_resamples, minimum: int = 1) -> int:
-    if not isinstance(n_resamples, (int, np.integer)) or isinstance(n_resamples, bool) or not minimum <= int(n_resamples) <= MAX_RESAMPLES:
-        raise ValueError(f"'n_resamples' must be an integer in [{minimum}, {MAX_RESAMPLES}].")
-    return int(n_resamples)
+    return _int_in_range(n_resamples, minimum, MAX_RESAMPLES, f"'n_resamples' must be an integer in [{minimum}, {MAX_RESAMPLES}].")
 
 
 def check_counts(X) -> np.ndarray:
@@ -54,9 +57,7 @@ def resample_counts(X, n_resamples: int, seed: int = 0, device: int = 0) -> np.n
     N, V = X.shape
     if N < 1 or not 1 <= V <= MAX_FEATURES:
         raise ValueError(f"Counts to resample need at least one row and 1 to {MAX_FEATURES} columns.")
-    lib = _lib.load()
-    if lib.salnmf_device_count() < 1:
-        raise _lib.EngineUnavailable("no HIP device visible: salamander_amd runs on MI355X (gfx950) only and has no CPU fallback.")
+    lib = _lib.load_with_device()
     out = np.empty((R, N, V), dtype=np.float64)
     _lib.check(lib.salnmf_resample_counts(int(device), _ptr(X), N, V, R, seed, _ptr(out)))
     return out

@@ -15,15 +15,13 @@ import numpy as np
 
 from . import _lib
 from .engine import _ptr
-from .resample import MAX_FEATURES, check_counts, check_seed
+from .resample import MAX_FEATURES, _int_in_range, check_counts, check_seed
 
 MAX_SPLITS = 32767
 
 
 def check_n_splits(n_splits, minimum: int = 1) -> int:
-    if not isinstance(n_splits, (int, np.integer)) or isinstance(n_splits, bool) or not minimum <= int(n_splits) <= MAX_SPLITS:
-        raise ValueError(f"'n_splits' must be an integer in [{minimum}, {MAX_SPLITS}].")
-    return int(n_splits)
+    return _int_in_range(n_splits, minimum, MAX_SPLITS, f"'n_splits' must be an integer in [{minimum}, {MAX_SPLITS}].")
 
 
 def train_threshold(train_fraction) -> int:

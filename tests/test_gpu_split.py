@@ -5,6 +5,7 @@ matrices exactly -- ``np.array_equal``, every entry of every case -- and the sam
 import numpy as np
 import pytest
 
+import _resample_ref
 import _split_ref as ref
 import salamander_amd as sal
 from salamander_amd.batch import BatchEngine
@@ -98,6 +99,32 @@ def test_batch_layout(V):
         assert np.array_equal(slot[:N, :V], np.maximum(X, EPSILON)) and (slot[N:] == 0).all() and (slot[:, V:] == 0).all()
         b.split(F, p, seed)
         assert np.array_equal(np.stack([b.download_dataset(d) for d in range(2 * F)]), want)
+    finally:
+        b.close()
+
+
+def test_the_profile_entry_points_time_the_kernel_and_leave_the_draw_in_the_slots():
+    """N = 17, V = 7: a pad row, pad columns and rows of more Philox blocks than lanes (T = 513 and T = 5 000).  The timed
+    launches rewrite the slots with the same bits, so after a profile call the batch holds what the draw itself leaves."""
+    N, V, seed = 17, 7, 2**40 + 3
+    rng = np.random.default_rng(V)
+    X = np.concatenate([edge_rows(V, rng), rng.poisson(rng.gamma(0.5, 20.0, size=(10, V))).astype(float)])
+    b = BatchEngine(N, V, [2])
+    try:
+        b.upload_X(X, clip=True)
+        ms = b.profile_split(3, 0.8, seed, n_calls=2)
+        assert np.isfinite(ms) and ms > 0
+        want = np.concatenate(ref.split_counts(X, 3, 0.8, seed))
+        for d in range(6):
+            assert np.array_equal(b.download_dataset(d), want[d]), d
+            slot = b.download_dataset(d, raw=True)
+            assert (slot[N:] == 0).all() and (slot[:, V:] == 0).all(), d  # pad rows and columns exactly 0
+        b.upload_X(X, clip=True)
+        ms = b.profile_resample(2, seed, n_calls=2)
+        assert np.isfinite(ms) and ms > 0
+        want = _resample_ref.resample_counts(X, 2, seed)
+        for d in range(2):
+            assert np.array_equal(b.download_dataset(d), want[d]), d
     finally:
         b.close()
 
