@@ -192,7 +192,8 @@ struct FusedParams {
 //   s  = (x - p') / (x + p')      x - p' is exact (Sterbenz)
 //   log(x/p) = k ln2 + log((1+s)/(1-s)) = k ln2 + 2s + s R(s^2), R fitted for this range
 // Measured against a long-double reference (tools/log_probe.hip): abs error <= 2e-14 over
-// |log| <= 460, relative error <= 1e-15 away from ratio = 1 and better than log(fl(x/p)) near it.
+// |log| <= 256 (beyond that the rounding of the result alone is 2.8e-14: half an ulp of a number in [256, 512)),
+// relative error <= 1e-15 away from ratio = 1 at any |log| and better than log(fl(x/p)) near it.
 // Callers guarantee the operands are in range with log_operand_ok().  Used by the per-sample KL (forward mode 1); the
 // objectives use log_pos below.
 __device__ __forceinline__ bool log_operand_ok(double v) {
