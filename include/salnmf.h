@@ -595,6 +595,40 @@ int salnmf_assign_signatures(int device, const double* counts, int64_t n_samples
                              double* dense_errors, int* dense_n_iterations, int* dense_converged, double* selection_frequency,
                              double* exposures_quantiles, double* exposures_mean, double* exposures_resampled, double* timings);
 
+/* salnmf_assign_signatures with candidate sets, required signatures and a re-addition pass.
+ * salnmf_assign_signatures is this call with candidates = NULL, required = NULL, readd = 0, and keeps its bits.
+ *   candidates  NULL (every signature), or n_samples x n_signatures bytes, nonzero = signature k is a candidate in sample n:
+ *               the set C_n, which must not be empty;
+ *   required    NULL (none), or n_samples x n_signatures bytes: the set R_n, a subset of C_n;
+ *   readd       0 or 1.
+ * The sets of sample n hold for its counts and for every resample of them.  Contract, per problem:
+ *   phase 0: A = C_n, h_k = (sum_v x_v) / |C_n| for k in C_n and exactly 0.0 elsewhere, solve (the dense_* outputs; with every
+ *   signature a candidate this is salnmf_assign_signatures' phase 0 bit for bit);
+ *   backward rounds as above, with the protected set starting as R_n: a required signature is never a candidate for removal,
+ *   its kl_increase stays NaN and its removal_round -1; the rounds stop when there is no candidate or one signature is left;
+ *   re-addition pass (readd = 1), after the rounds have ended with (A, h, f): the pool is C_n \ A, each member tried at most
+ *   once.  At the accepted h every pool member has the update factor u_k = sum_v W[k, v] x_v / (h W)_v, the step's own factor;
+ *   u_k <= 1 is the KKT condition of a zero entry.  The candidate c is the untried pool member of largest u_k (strictly
+ *   larger than every one before it in ascending k, so the lowest index wins on equal values and a NaN never wins).  If there
+ *   is none, or not u_c > 1, the procedure ends.  Trial: copy h, set entry c to (sum_v x_v) / |C_n|, solve with A + {c}: h', f'.
+ *   If f - f' > max_kl_increase (false for a NaN) A, h, f become the trial's, otherwise they stay; either way c is tried.  There
+ *   is no second backward pass, so a problem sees at most (n_signatures - 1) + n_signatures trials.
+ * Further outputs, n_samples x n_signatures, both may be NULL when readd is 0 and are not written then: readd_round (the
+ * 0-based number, continuing the backward count, of the trial that re-added k, -1 otherwise) and kl_decrease (f - f' of the
+ * re-addition trial of k, NaN if never tried).  n_trials, n_iterations and converged cover both passes; removal_round keeps the
+ * round that removed k even where k is re-added: active and exposures tell the final state.
+ * Validated on the host before any launch, with everything else: a sample without a candidate, a required signature that is
+ * not a candidate, readd other than 0 or 1. */
+int salnmf_assign_signatures_ex(int device, const double* counts, int64_t n_samples, int n_features, const double* signatures,
+                                int n_signatures, int n_resamples, uint64_t seed, int n_quantiles, const double* quantiles,
+                                int min_iterations, int max_iterations, int conv_test_freq, double tol, double max_kl_increase,
+                                int64_t chunk_bytes, const uint8_t* candidates, const uint8_t* required, int readd,
+                                double* exposures, int* active, double* errors, int* removal_round, double* kl_increase,
+                                int* n_trials, int64_t* n_iterations, int* converged, double* dense_exposures,
+                                double* dense_errors, int* dense_n_iterations, int* dense_converged, double* selection_frequency,
+                                double* exposures_quantiles, double* exposures_mean, double* exposures_resampled,
+                                int* readd_round, double* kl_decrease, double* timings);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_int, c_int64, c_uint64, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_int, c_int64, c_uint8, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (SALNMF_LIB: a development hook of this loader -- tools/ A/B runs of two builds of the library in one gpurun call)
@@ -136,6 +136,9 @@ SIGNATURES = {
     # sparse assignment to fixed signatures: salamander_amd/assign.py
     "salnmf_assign_signatures": (c_int, [c_int, _D, c_int64, c_int, _D, c_int, c_int, c_uint64, c_int, _D, c_int, c_int, c_int, c_double, c_double, c_int64,
                                          _D, _I, _D, _I, _D, _I, POINTER(c_int64), _I, _D, _D, _I, _I, _D, _D, _D, _D, _D]),
+    "salnmf_assign_signatures_ex": (c_int, [c_int, _D, c_int64, c_int, _D, c_int, c_int, c_uint64, c_int, _D, c_int, c_int, c_int, c_double, c_double, c_int64,
+                                            POINTER(c_uint8), POINTER(c_uint8), c_int,
+                                            _D, _I, _D, _I, _D, _I, POINTER(c_int64), _I, _D, _D, _I, _I, _D, _D, _D, _D, _I, _D, _D]),
 }
 
 OBJECTIVE_SLOTS = 256  # SALNMF_OBJECTIVE_SLOTS
@@ -216,10 +219,10 @@ def load_with_device():
 
 
 def pointer(a):
-    """The argument a float64, int32 or int64 array is passed as; null for ``None`` and for an empty array."""
+    """The argument a float64, int32, int64 or uint8 array is passed as; null for ``None`` and for an empty array."""
     if a is None or a.size == 0:
         return None
-    types = {"float64": _D, "int32": _I, "int64": POINTER(c_int64)}
+    types = {"float64": _D, "int32": _I, "int64": POINTER(c_int64), "uint8": POINTER(c_uint8)}
     if a.dtype.name not in types:
         raise TypeError(f"no pointer type for an array of {a.dtype.name}")
     return a.ctypes.data_as(types[a.dtype.name])

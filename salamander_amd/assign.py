@@ -8,6 +8,10 @@ sample's KL divergence rose by at most ``max_kl_increase``, otherwise the signat
 ``n_resamples = R > 0`` the whole procedure also runs for R bootstrap resamples of the counts and the device reduces them to
 a selection frequency per (sample, signature) and to the mean and order statistics of the exposures, zeros included.  There
 is no CPU fallback.
+
+``candidates`` restricts the catalogue per sample (the start value and every solve see the candidate signatures only),
+``required`` names signatures that are never tried for removal, and ``readd=True`` follows the backward rounds with a
+re-addition pass over the removed candidates, all inside the same kernel launch.
 """
 
 from __future__ import annotations
@@ -44,17 +48,53 @@ class AssignResult:
     quantiles: tuple = ()
     max_kl_increase: float = 1.92
     timings: dict = field(default_factory=dict)
+    readd_round: np.ndarray | None = None  # (N, K) int32 with readd: the 0-based trial that re-added k, -1 otherwise
+    kl_decrease: np.ndarray | None = None  # (N, K) with readd: f - f' of the re-addition trial of k, NaN if never tried
+    candidates: np.ndarray | None = None  # (N, K) bool as applied, None = every signature
+    required: np.ndarray | None = None  # (N, K) bool as applied, None = none
+
+
+def check_sets(candidates, required, readd, N: int, K: int):
+    """The two masks as ``(N, K)`` bool arrays (or ``None``) and ``readd`` as a bool, or ``ValueError``: each mask is ``None``, a
+    boolean array of shape ``(K,)`` for every sample, or one of shape ``(N, K)``; every sample needs a candidate, and a
+    required signature must be a candidate."""
+    def mask(name, value):
+        if value is None:
+            return None
+        m = np.asarray(value)
+        if m.dtype != np.bool_:
+            raise ValueError(f"'{name}' must be a boolean array, got dtype {m.dtype}.")
+        if m.shape == (K,):
+            m = np.broadcast_to(m, (N, K))
+        elif m.shape != (N, K):
+            raise ValueError(f"'{name}' must have shape ({K},) or ({N}, {K}), got {m.shape}.")
+        return np.ascontiguousarray(m)
+
+    if not isinstance(readd, (bool, np.bool_)):
+        raise ValueError("'readd' must be True or False.")
+    C, Rq = mask("candidates", candidates), mask("required", required)
+    if C is not None and not C.any(axis=1).all():
+        raise ValueError(f"Sample {int(np.flatnonzero(~C.any(axis=1))[0])} has no candidate signature.")
+    if C is not None and Rq is not None and (Rq & ~C).any():
+        n, k = np.argwhere(Rq & ~C)[0]
+        raise ValueError(f"Sample {int(n)}: required signature {int(k)} is not a candidate.")
+    return C, Rq, bool(readd)
 
 
 def assign_signatures(counts, signatures, max_kl_increase: float = 1.92, n_resamples: int = 0, resample_seed: int = 0,
                       quantiles=(0.025, 0.5, 0.975), min_iterations: int = 500, max_iterations: int = 10000, conv_test_freq: int = 10,
-                      tol: float = 1e-7, keep_resamples: bool = False, device: int = 0, chunk_bytes: int | None = None) -> AssignResult:
+                      tol: float = 1e-7, keep_resamples: bool = False, device: int = 0, chunk_bytes: int | None = None,
+                      candidates=None, required=None, readd: bool = False) -> AssignResult:
     """Sparse exposures of every row of ``counts (N, V)`` to the fixed ``signatures (K, V)``, K <= 96 and V <= 96.
 
     Arguments as :func:`refit_exposures`.  ``max_kl_increase`` is the largest rise of a sample's KL divergence a removal may
     cost; the KL difference is the Poisson log-likelihood difference, so the default 1.92 is half the 95 % point of a
     chi-square with one degree of freedom -- a parameter, not a measurement.  ``max_iterations`` must be a multiple of
-    ``conv_test_freq``.  Anything out of range is a ``ValueError`` before the device is touched."""
+    ``conv_test_freq``.  ``candidates`` and ``required`` are ``None`` or boolean masks of shape (K,) or (N, K): the signatures a
+    sample may use at all, and those of them that are never tried for removal; they hold for the sample's resamples too.
+    ``readd=True`` adds the re-addition pass: removed candidates whose update factor exceeds 1 at the accepted exposures are
+    tried again, largest factor first, and kept if the KL divergence falls by more than ``max_kl_increase``.  Anything out of
+    range is a ``ValueError`` before the device is touched."""
     t_start = time.perf_counter()
     X, S, R, seed, min_it, max_it, freq, tol, q, chunk = check_arguments(counts, signatures, n_resamples, resample_seed, quantiles, min_iterations,
                                                                          max_iterations, conv_test_freq, tol, chunk_bytes)
@@ -64,6 +104,7 @@ def assign_signatures(counts, signatures, max_kl_increase: float = 1.92, n_resam
         raise ValueError("'max_kl_increase' must be a finite number.")
     thr = float(max_kl_increase)
     (N, V), K = X.shape, S.shape[0]
+    C, Rq, readd = check_sets(candidates, required, readd, N, K)
     lib = _lib.load_with_device()
 
     Q = int(q.size)
@@ -76,16 +117,21 @@ def assign_signatures(counts, signatures, max_kl_increase: float = 1.92, n_resam
     Hq = f64(Q, N, K) if R else None
     Hm = f64(N, K) if R else None
     Hr = f64(R, N, K) if R and keep_resamples else None
+    rrnd = i32(N, K) if readd else None
+    kld = f64(N, K) if readd else None
+    Cb = None if C is None else C.astype(np.uint8)
+    Rb = None if Rq is None else Rq.astype(np.uint8)
     ms = (c_double * 4)()
     p = _lib.pointer
-    _lib.check(lib.salnmf_assign_signatures(
-        int(device), p(X), N, V, p(S), K, R, seed, Q if R else 0, p(q), min_it, max_it, freq, tol, thr, chunk,
+    _lib.check(lib.salnmf_assign_signatures_ex(
+        int(device), p(X), N, V, p(S), K, R, seed, Q if R else 0, p(q), min_it, max_it, freq, tol, thr, chunk, p(Cb), p(Rb), int(readd),
         p(H), p(act), p(err), p(rnd), p(kl), p(ntr), p(nit), p(conv), p(Hd), p(err_d), p(nit_d), p(conv_d), p(sel), p(Hq), p(Hm), p(Hr),
-        ctypes.cast(ms, _lib._D),
+        p(rrnd), p(kld), ctypes.cast(ms, _lib._D),
     ))
     timings = {"resample_s": ms[0] / 1e3, "assign_s": ms[1] / 1e3, "reduce_s": ms[2] / 1e3, "assign_kernel_ms": ms[1],
                "n_chunks": int(ms[3]), "total_s": time.perf_counter() - t_start}
     return AssignResult(exposures=H, active=act.astype(bool), reconstruction_errors=err, removal_round=rnd, kl_increase=kl, n_trials=ntr,
                         n_iterations=nit, converged=conv.astype(bool), dense_exposures=Hd, dense_errors=err_d, dense_n_iterations=nit_d,
                         dense_converged=conv_d.astype(bool), selection_frequency=sel, exposures_quantiles=Hq, exposures_mean=Hm,
-                        exposures_resampled=Hr, quantiles=tuple(float(v) for v in q), max_kl_increase=thr, timings=timings)
+                        exposures_resampled=Hr, quantiles=tuple(float(v) for v in q), max_kl_increase=thr, timings=timings, readd_round=rrnd,
+                        kl_decrease=kld, candidates=C, required=Rq)

@@ -19,6 +19,17 @@
 // lane -- so the loop carries one h, not two.  The sets are bit masks held alike by the four lanes of a column.  Branches
 // are taken on ballots, the transitions inside them are predicated per column; a column's numbers never meet another
 // column's (salnmf_refit.h), so a problem's result depends on nothing but its row and W.
+//
+// assign_kernel<KT, true> adds candidate sets, required signatures and the re-addition pass; the
+// <KT, false> instantiations are the kernel above, statement for statement.  The act / prot words start from two optional
+// per-sample arrays (problem p reads row p % N: a resample shares its sample's sets) and the start value divides by the
+// population count of the candidate words.  A third set, `tried`, starts as the complement of the candidates, so the pool of
+// the re-addition pass is ~act & ~tried.  Two more modes: 4, the column waits for its next re-addition candidate, and 3, a
+// re-addition trial.  A column whose backward rounds are over (or whose re-addition trial has been decided) goes to mode 4
+// and asks for a re-pass; there P^T is that of the accepted h (reloaded after a rejection), the update factors U are
+// computed from it as a step computes them, and the column takes the pool member of largest U, lowest index on equal values
+// -- lane-local in ascending k, then two __shfl_xor steps, as the arg-min.  If U > 1 its entry is set to sum(x) / |C| and
+// the solve starts (mode 3, one more re-pass for its iteration-0 test), otherwise the column is finished.
 #pragma once
 #include "salnmf_refit.h"
 
@@ -44,6 +55,13 @@ struct AssignArgs {
     int V, K;
     int min_it, max_it, freq;      // max_it % freq == 0
     double tol, thr;
+    // assign_kernel<KT, true> alone reads what follows
+    const unsigned* __restrict__ cand;  // [N][NW] candidate words of sample n, NW = (KT + 1) / 2; or null: all K
+    const unsigned* __restrict__ req;   // [N][NW] required words (a subset of cand); or null: none
+    int* __restrict__ rround;           // [P][K]: the trial that re-added k, -1 otherwise; or null
+    double* __restrict__ kld;           // [P][K]: f - f' of the re-addition trial of k, NaN if never tried; or null
+    int64_t N;                          // rows of cand / req: problem p reads row p % N
+    int readd;
 };
 
 struct AssignSelectArgs {
@@ -55,7 +73,22 @@ struct AssignSelectArgs {
 
 #ifdef SALNMF_REFIT_KERNELS
 
+// U^T of a step from its P^T (the loop below has the same statements in line): the update factors at h
 template <int KT>
+__device__ __forceinline__ void assign_update_factors(const double (&x)[VT][4], const d4 (&pr)[VT], const double* wu, int V, int q, d4 (&u)[KT]) {
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt) u[kt] = (d4){0, 0, 0, 0};
+#pragma unroll
+    for (int vt = 0; vt < VT; ++vt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const double av = (16 * vt + 4 * r + q < V) ? div_path(x[vt][r], pr[vt][r]) : 0.0;
+#pragma unroll
+            for (int kt = 0; kt < KT; ++kt) u[kt] = mfma(wu[16 * kt * WS + 4 * (4 * vt + r)], av, u[kt]);
+        }
+}
+
+template <int KT, bool EX>
 __global__ void __launch_bounds__(BLOCK) assign_kernel(AssignArgs a) {
     constexpr int KP = 16 * KT;
     constexpr int NW = (KT + 1) / 2;  // 32-bit words of a signature set
@@ -93,22 +126,40 @@ __global__ void __launch_bounds__(BLOCK) assign_kernel(AssignArgs a) {
                 t += x[vt][r];
             }
         t = rows_sum(t);
-        d4 h[KT];
-#pragma unroll
-        for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) h[kt][r] = (16 * kt + 4 * r + q < K) ? t / (double)K : 0.0;
-
         // the column's state, the same in its four lanes.  A lane column past the end of the list is finished from the start:
         // it recomputes the last problem's first step and touches no memory.
         unsigned act[NW], prot[NW];
+        [[maybe_unused]] unsigned tried[NW];  // EX: tried for re-addition, or no candidate at all
+        [[maybe_unused]] double h0 = 0.0;     // EX: sum(x) / |C|
 #pragma unroll
         for (int w = 0; w < NW; ++w) {
             const int n = K - 32 * w;
             act[w] = n >= 32 ? ~0u : n > 0 ? (1u << n) - 1u : 0u;
             prot[w] = 0u;
         }
-        int mode = p < a.P ? 0 : 2;  // 0: phase 0, 1: a trial, 2: finished
+        d4 h[KT];
+        if constexpr (EX) {
+            const int64_t mrow = (row % a.N) * NW;
+            int nc = 0;
+#pragma unroll
+            for (int w = 0; w < NW; ++w) {
+                if (a.cand) act[w] &= a.cand[mrow + w];
+                if (a.req) prot[w] = a.req[mrow + w] & act[w];
+                tried[w] = ~act[w];
+                nc += __popc(act[w]);
+            }
+            h0 = t / (double)nc;
+#pragma unroll
+            for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) h[kt][r] = ((act[kt >> 1] >> ((16 * kt + 4 * r + q) & 31)) & 1u) ? h0 : 0.0;
+        } else {
+#pragma unroll
+            for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) h[kt][r] = (16 * kt + 4 * r + q < K) ? t / (double)K : 0.0;
+        }
+        int mode = p < a.P ? 0 : 2;  // 0: phase 0, 1: a trial, 2: finished; EX: 3: a re-addition trial, 4: waits for its candidate
         bool fresh = false;          // the solve has just started: its iteration-0 test is due
         int itl = 0, cand = 0, ntr = 0, conv = 1;
         long long nsum = 0;
@@ -122,6 +173,33 @@ __global__ void __launch_bounds__(BLOCK) assign_kernel(AssignArgs a) {
                     if (k < K) a.kl[p * K + k] = __builtin_nan(""), a.round[p * K + k] = -1;
                 }
         }
+        if constexpr (EX) {
+            if (mode == 0 && a.kld) {
+#pragma unroll
+                for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int k = 16 * kt + 4 * r + q;
+                        if (k < K) a.kld[p * K + k] = __builtin_nan(""), a.rround[p * K + k] = -1;
+                    }
+            }
+        }
+        // the column is through: its sets and sums go out (predicated)
+        auto finish = [&](bool who) {
+            if (who) {
+                mode = 2;
+                if (a.active) {
+#pragma unroll
+                    for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int k = 16 * kt + 4 * r + q;
+                            if (k < K) a.active[p * K + k] = (int)((act[kt >> 1] >> (k & 31)) & 1u);
+                        }
+                }
+                if (q == 0) a.err[p] = f, a.nit[p] = nsum, a.conv[p] = conv, a.ntrials[p] = ntr;
+            }
+        };
 
         int until_test = 0;   // steps until the next multiple of conv_test_freq (uniform)
         bool repass = false;  // this pass of the body follows a transition without a step (uniform)
@@ -145,10 +223,11 @@ __global__ void __launch_bounds__(BLOCK) assign_kernel(AssignArgs a) {
                     prev = cur;
                 }
                 fresh = false;
+                [[maybe_unused]] const bool select = EX && mode == 4;  // (asked for this re-pass: P^T is that of the accepted h)
                 if (__any(stop)) {
-                    const bool dense = stop && mode == 0, trial = stop && mode == 1;
-                    const double delta = cur - f;
-                    const bool accept = dense || (trial && delta <= a.thr), reject = trial && !accept;
+                    const bool dense = stop && mode == 0, trial = stop && mode == 1, add = EX && stop && mode == 3;
+                    const double delta = add ? f - cur : cur - f;
+                    const bool accept = dense || (trial && delta <= a.thr) || (add && delta > a.thr), reject = (trial || add) && !accept;
                     const bool owner = q == (cand & 3);
                     if (stop) nsum += itl, conv &= cv;
                     if (dense && a.dH) {
@@ -171,7 +250,19 @@ __global__ void __launch_bounds__(BLOCK) assign_kernel(AssignArgs a) {
 #pragma unroll
                         for (int w = 0; w < NW; ++w) prot[w] |= (cand >> 5) == w ? 1u << (cand & 31) : 0u;
                     }
-                    if (trial) ++ntr;
+                    if constexpr (EX) {
+                        if (add && owner && a.kld) a.kld[p * K + cand] = delta;
+                        if (add && accept && owner && a.rround) a.rround[p * K + cand] = ntr;
+                        if (add) {
+#pragma unroll
+                            for (int w = 0; w < NW; ++w) {
+                                const unsigned bit = (cand >> 5) == w ? 1u << (cand & 31) : 0u;
+                                tried[w] |= bit;
+                                act[w] |= accept ? bit : 0u;
+                            }
+                        }
+                    }
+                    if (trial || add) ++ntr;
                     if (accept) f = cur;
 #pragma unroll
                     for (int kt = 0; kt < KT; ++kt)
@@ -202,19 +293,11 @@ __global__ void __launch_bounds__(BLOCK) assign_kernel(AssignArgs a) {
                         const int oi = __shfl_xor(bi, m);
                         if (ov < bv || (ov == bv && oi < bi)) bv = ov, bi = oi;
                     }
-                    const bool more = stop && bi != NONE && left > 1;
-                    if (stop && !more) {
-                        mode = 2;
-                        if (a.active) {
-#pragma unroll
-                            for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-                                for (int r = 0; r < 4; ++r) {
-                                    const int k = 16 * kt + 4 * r + q;
-                                    if (k < K) a.active[p * K + k] = (int)((act[kt >> 1] >> (k & 31)) & 1u);
-                                }
-                        }
-                        if (q == 0) a.err[p] = f, a.nit[p] = nsum, a.conv[p] = conv, a.ntrials[p] = ntr;
+                    const bool more = stop && !add && bi != NONE && left > 1;
+                    if (EX && a.readd) {
+                        if (stop && !more) mode = 4;
+                    } else {
+                        finish(stop && !more);
                     }
                     if (more) {
                         cand = bi, mode = 1, itl = 0, fresh = true;
@@ -225,8 +308,43 @@ __global__ void __launch_bounds__(BLOCK) assign_kernel(AssignArgs a) {
                                 if (16 * kt + 4 * r + q == bi) h[kt][r] = 0.0;
                     }
                 }
+                if constexpr (EX) {
+                    if (__any(select)) {
+                        // the next re-addition candidate: largest update factor in the pool, lowest index on ties
+                        d4 u[KT];
+                        assign_update_factors<KT>(x, pr, wu, V, q, u);
+                        unsigned el[NW];
+#pragma unroll
+                        for (int w = 0; w < NW; ++w) el[w] = (~act[w] & ~tried[w]) >> q;
+                        double bv = -__builtin_inf();
+                        int bi = NONE;
+#pragma unroll
+                        for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                const bool ok = (el[kt >> 1] >> (16 * (kt & 1) + 4 * r)) & 1u;
+                                if (ok && u[kt][r] > bv) bv = u[kt][r], bi = 16 * kt + 4 * r + q;
+                            }
+#pragma unroll
+                        for (int m = 16; m <= 32; m <<= 1) {
+                            const double ov = __shfl_xor(bv, m);
+                            const int oi = __shfl_xor(bi, m);
+                            if (ov > bv || (ov == bv && oi < bi)) bv = ov, bi = oi;
+                        }
+                        const bool go = select && bi != NONE && bv > 1.0;
+                        finish(select && !go);
+                        if (go) {
+                            cand = bi, mode = 3, itl = 0, fresh = true;
+#pragma unroll
+                            for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+                                for (int r = 0; r < 4; ++r)
+                                    if (16 * kt + 4 * r + q == bi) h[kt][r] = h0;
+                        }
+                    }
+                }
                 if (__all(mode == 2)) break;
-                if (__any(fresh)) {
+                if (__any(fresh || (EX && mode == 4))) {
                     repass = true;
                     continue;
                 }

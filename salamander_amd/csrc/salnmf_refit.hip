@@ -1,6 +1,7 @@
 // Host side of the refit to fixed signatures (include/salnmf.h: salnmf_refit_exposures) and its two kernels
 // (salnmf_refit.h: refit_kernel, refit_reduce_kernel); and of the sparse assignment built on it
-// (salnmf_assign_signatures; salnmf_assign.h: assign_kernel, assign_selection_kernel), DESIGN.md section 14.
+// (salnmf_assign_signatures, salnmf_assign_signatures_ex; salnmf_assign.h: assign_kernel, assign_selection_kernel), DESIGN.md sections 14
+// and 14.1.
 #define SALNMF_TEMPLATES_ONLY 1
 #define SALNMF_REFIT_KERNELS 1
 #include "../../include/salnmf.h"
@@ -22,12 +23,21 @@ namespace {
 struct RefitInputs {
     std::vector<double> x;
     std::vector<uint32_t> icounts;
+    std::vector<uint32_t> cand, req;  // the assignment's sets as [N][words] bit masks; empty where the argument is null
     RefitReduceArgs red{};
     int cus = 0;
 };
 
+// The assignment's optional sets: one byte per (sample, signature), anything but 0 is "set".
+struct AssignSets {
+    const uint8_t* candidates = nullptr;
+    const uint8_t* required = nullptr;
+    int readd = 0;
+};
+
 int refit_prepare(int device, const double* counts, int64_t N, int V, const double* signatures, int K, int R, int Q, const double* quantiles,
-                  int min_iterations, int max_iterations, int conv_test_freq, double tol, bool resample_outputs, RefitInputs& in) {
+                  int min_iterations, int max_iterations, int conv_test_freq, double tol, bool resample_outputs, RefitInputs& in,
+                  const AssignSets& sets = AssignSets{}) {
     if (N < 1 || N > 0x7fffffff) return fail("n_samples must be in [1, 2^31), got %lld", (long long)N);
     if (V < 1 || V > VMAX) return fail("n_features must be in [1, %d], got %d", VMAX, V);
     if (K < 1 || K > REFIT_KMAX) return fail("n_signatures must be in [1, %d], got %d", REFIT_KMAX, K);
@@ -37,6 +47,31 @@ int refit_prepare(int device, const double* counts, int64_t N, int V, const doub
     if (!(tol >= 0.0) || !std::isfinite(tol)) return fail("tol must be finite and not negative, got %g", tol);
     if (Q < 0 || Q > REFIT_MAX_QUANTILES) return fail("n_quantiles must be in [0, %d], got %d", REFIT_MAX_QUANTILES, Q);
     if (R > 0 && !resample_outputs) return fail("null output for the resamples");
+    if (sets.readd != 0 && sets.readd != 1) return fail("readd must be 0 or 1, got %d", sets.readd);
+    const int words = ((K + 15) / 16 + 1) / 2;  // assign_kernel<KT>: NW
+    auto pack = [&](const uint8_t* set, std::vector<uint32_t>& out) {
+        out.assign((size_t)N * words, 0u);
+        for (int64_t n = 0; n < N; ++n)
+            for (int k = 0; k < K; ++k)
+                if (set[(size_t)n * K + k]) out[(size_t)n * words + (k >> 5)] |= 1u << (k & 31);
+    };
+    if (sets.candidates) {
+        pack(sets.candidates, in.cand);
+        for (int64_t n = 0; n < N; ++n) {
+            uint32_t any = 0u;
+            for (int w = 0; w < words; ++w) any |= in.cand[(size_t)n * words + w];
+            if (!any) return fail("sample %lld has no candidate signature", (long long)n);
+        }
+    }
+    if (sets.required) {
+        pack(sets.required, in.req);
+        if (sets.candidates)
+            for (size_t i = 0; i < in.req.size(); ++i)
+                if (in.req[i] & ~in.cand[i]) {
+                    const uint32_t off = in.req[i] & ~in.cand[i];
+                    return fail("sample %lld: required signature %d is not a candidate", (long long)(i / words), 32 * (int)(i % words) + __builtin_ctz(off));
+                }
+    }
     for (int k = 0; k < K; ++k) {
         double sum = 0.0;
         for (int v = 0; v < V; ++v) {
@@ -91,13 +126,21 @@ int launch_assign(const AssignArgs& a, int cus, hipStream_t stream) {
     const int64_t ntiles = (a.P + 15) / 16;
     const dim3 grid((unsigned)std::min<int64_t>((int64_t)cus, (ntiles + WAVES - 1) / WAVES));  // as launch_refit
     HIPCK(hipMemsetAsync(a.next_tile, 0, sizeof(unsigned), stream));
-    switch ((a.K + 15) / 16) {
-        case 1: hipLaunchKernelGGL(assign_kernel<1>, grid, dim3(BLOCK), 0, stream, a); break;
-        case 2: hipLaunchKernelGGL(assign_kernel<2>, grid, dim3(BLOCK), 0, stream, a); break;
-        case 3: hipLaunchKernelGGL(assign_kernel<3>, grid, dim3(BLOCK), 0, stream, a); break;
-        case 4: hipLaunchKernelGGL(assign_kernel<4>, grid, dim3(BLOCK), 0, stream, a); break;
-        case 5: hipLaunchKernelGGL(assign_kernel<5>, grid, dim3(BLOCK), 0, stream, a); break;
-        case 6: hipLaunchKernelGGL(assign_kernel<6>, grid, dim3(BLOCK), 0, stream, a); break;
+    // candidate sets, required signatures and the re-addition pass have instantiations of their own
+    const int kt = (a.K + 15) / 16 + (a.cand || a.req || a.readd ? 8 : 0);
+    switch (kt) {
+        case 1: hipLaunchKernelGGL((assign_kernel<1, false>), grid, dim3(BLOCK), 0, stream, a); break;
+        case 2: hipLaunchKernelGGL((assign_kernel<2, false>), grid, dim3(BLOCK), 0, stream, a); break;
+        case 3: hipLaunchKernelGGL((assign_kernel<3, false>), grid, dim3(BLOCK), 0, stream, a); break;
+        case 4: hipLaunchKernelGGL((assign_kernel<4, false>), grid, dim3(BLOCK), 0, stream, a); break;
+        case 5: hipLaunchKernelGGL((assign_kernel<5, false>), grid, dim3(BLOCK), 0, stream, a); break;
+        case 6: hipLaunchKernelGGL((assign_kernel<6, false>), grid, dim3(BLOCK), 0, stream, a); break;
+        case 9: hipLaunchKernelGGL((assign_kernel<1, true>), grid, dim3(BLOCK), 0, stream, a); break;
+        case 10: hipLaunchKernelGGL((assign_kernel<2, true>), grid, dim3(BLOCK), 0, stream, a); break;
+        case 11: hipLaunchKernelGGL((assign_kernel<3, true>), grid, dim3(BLOCK), 0, stream, a); break;
+        case 12: hipLaunchKernelGGL((assign_kernel<4, true>), grid, dim3(BLOCK), 0, stream, a); break;
+        case 13: hipLaunchKernelGGL((assign_kernel<5, true>), grid, dim3(BLOCK), 0, stream, a); break;
+        case 14: hipLaunchKernelGGL((assign_kernel<6, true>), grid, dim3(BLOCK), 0, stream, a); break;
         default: return fail("no assignment kernel for %d signatures", a.K);
     }
     HIPCK(hipGetLastError());
@@ -234,18 +277,34 @@ extern "C" int salnmf_assign_signatures(int device, const double* counts, int64_
                                         double* dense_exposures, double* dense_errors, int* dense_n_iterations, int* dense_converged,
                                         double* selection_frequency, double* exposures_quantiles, double* exposures_mean, double* exposures_resampled,
                                         double* timings) {
+    return salnmf_assign_signatures_ex(device, counts, n_samples, n_features, signatures, n_signatures, n_resamples, seed, n_quantiles, quantiles,
+                                       min_iterations, max_iterations, conv_test_freq, tol, max_kl_increase, chunk_bytes, nullptr, nullptr, 0, exposures,
+                                       active, errors, removal_round, kl_increase, n_trials, n_iterations, converged, dense_exposures, dense_errors,
+                                       dense_n_iterations, dense_converged, selection_frequency, exposures_quantiles, exposures_mean, exposures_resampled,
+                                       nullptr, nullptr, timings);
+}
+
+extern "C" int salnmf_assign_signatures_ex(int device, const double* counts, int64_t n_samples, int n_features, const double* signatures, int n_signatures,
+                                           int n_resamples, uint64_t seed, int n_quantiles, const double* quantiles, int min_iterations,
+                                           int max_iterations, int conv_test_freq, double tol, double max_kl_increase, int64_t chunk_bytes,
+                                           const uint8_t* candidates, const uint8_t* required, int readd, double* exposures, int* active, double* errors,
+                                           int* removal_round, double* kl_increase, int* n_trials, int64_t* n_iterations, int* converged,
+                                           double* dense_exposures, double* dense_errors, int* dense_n_iterations, int* dense_converged,
+                                           double* selection_frequency, double* exposures_quantiles, double* exposures_mean,
+                                           double* exposures_resampled, int* readd_round, double* kl_decrease, double* timings) {
     const int64_t N = n_samples;
     const int V = n_features, K = n_signatures, R = n_resamples, Q = n_quantiles;
     if (!counts || !signatures || !exposures || !active || !errors || !removal_round || !kl_increase || !n_trials || !n_iterations || !converged ||
         !dense_exposures || !dense_errors || !dense_n_iterations || !dense_converged)
         return fail("null argument");
+    if (readd == 1 && (!readd_round || !kl_decrease)) return fail("null output for the re-addition pass");
     if (!std::isfinite(max_kl_increase)) return fail("max_kl_increase must be finite, got %g", max_kl_increase);
     // (solves follow one another inside one wave, and the tests of its 16 problems must fall on the same iterations)
     if (conv_test_freq >= 1 && max_iterations >= 0 && max_iterations % conv_test_freq != 0)
         return fail("max_iterations must be a multiple of conv_test_freq, got %d and %d", max_iterations, conv_test_freq);
     RefitInputs in;
     CK(refit_prepare(device, counts, N, V, signatures, K, R, Q, quantiles, min_iterations, max_iterations, conv_test_freq, tol,
-                     selection_frequency && exposures_mean && (Q <= 0 || (quantiles && exposures_quantiles)), in));
+                     selection_frequency && exposures_mean && (Q <= 0 || (quantiles && exposures_quantiles)), in, AssignSets{candidates, required, readd}));
     const int cus = in.cus;
     const int64_t budget = chunk_bytes > 0 ? chunk_bytes : (int64_t)256 << 20;
     const int chunk = R > 0 ? (int)std::max<int64_t>(1, std::min<int64_t>(R, budget / (int64_t)(sizeof(double) * (size_t)N * V))) : 0;
@@ -270,6 +329,15 @@ extern "C" int salnmf_assign_signatures(int device, const double* counts, int64_
     unsigned* dnext = d.get<unsigned>(1);
     if (!dW || !dX || !dH || !dHd || !dkl || !dact || !dround || !derr || !derr_d || !dnit || !dconv || !dntr || !dnit_d || !dconv_d || !dnext)
         return fail("hipMalloc failed (assignment of %lld samples)", (long long)N);
+    uint32_t *dcand = nullptr, *dreq = nullptr;
+    int* drround = nullptr;
+    double* dkld = nullptr;
+    if (candidates) dcand = d.get<uint32_t>(in.cand.size());
+    if (required) dreq = d.get<uint32_t>(in.req.size());
+    if (readd) drround = d.get<int>(NK), dkld = d.get<double>(NK);
+    if ((candidates && !dcand) || (required && !dreq) || (readd && (!drround || !dkld))) return fail("hipMalloc failed (sets of %lld samples)", (long long)N);
+    if (dcand) HIPCK(hipMemcpyAsync(dcand, in.cand.data(), in.cand.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+    if (dreq) HIPCK(hipMemcpyAsync(dreq, in.req.data(), in.req.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
     uint32_t* dcounts = nullptr;
     double *dXr = nullptr, *dHr = nullptr, *derr_r = nullptr, *dquant = nullptr, *dmean = nullptr, *dfreq = nullptr;
     long long* dnit_r = nullptr;
@@ -293,7 +361,7 @@ extern "C" int salnmf_assign_signatures(int device, const double* counts, int64_
     HIPCK(hipMemcpyAsync(dX, in.x.data(), in.x.size() * sizeof(double), hipMemcpyHostToDevice, d.stream));
 
     AssignArgs a{dX, dW, dH, derr, dnit, dconv, dntr, dact, dround, dkl, dHd, derr_d, dnit_d, dconv_d, dnext, N, V, K,
-                 min_iterations, max_iterations, conv_test_freq, tol, max_kl_increase};
+                 min_iterations, max_iterations, conv_test_freq, tol, max_kl_increase, dcand, dreq, drround, dkld, N, readd};
     std::vector<std::pair<hipEvent_t, hipEvent_t>> spans[3];  // resample, assign, reduce
     auto timed = [&](int which, auto&& body) -> int {
         hipEvent_t e0 = timings ? d.mark() : nullptr;
@@ -321,7 +389,7 @@ extern "C" int salnmf_assign_signatures(int device, const double* counts, int64_
         c.nit = dnit_r + (size_t)first * N;
         c.conv = dconv_r + (size_t)first * N;
         c.ntrials = dntr_r + (size_t)first * N;
-        c.active = nullptr, c.round = nullptr, c.kl = nullptr;
+        c.active = nullptr, c.round = nullptr, c.kl = nullptr, c.rround = nullptr, c.kld = nullptr;
         c.dH = nullptr, c.derr = nullptr, c.dnit = nullptr, c.dconv = nullptr;
         CK(timed(1, [&] { return launch_assign(c, cus, d.stream); }));
     }
@@ -353,6 +421,10 @@ extern "C" int salnmf_assign_signatures(int device, const double* counts, int64_
     HIPCK(hipMemcpyAsync(active, dact, NK * sizeof(int), hipMemcpyDeviceToHost, d.stream));
     HIPCK(hipMemcpyAsync(removal_round, dround, NK * sizeof(int), hipMemcpyDeviceToHost, d.stream));
     HIPCK(hipMemcpyAsync(kl_increase, dkl, NK * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    if (readd) {
+        HIPCK(hipMemcpyAsync(readd_round, drround, NK * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+        HIPCK(hipMemcpyAsync(kl_decrease, dkld, NK * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    }
     HIPCK(hipMemcpyAsync(errors, derr, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, d.stream));
     HIPCK(hipMemcpyAsync(n_trials, dntr, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, d.stream));
     HIPCK(hipMemcpyAsync(n_iterations, dnit, (size_t)N * sizeof(int64_t), hipMemcpyDeviceToHost, d.stream));
