@@ -1095,259 +1095,11 @@ static int check_abort(salnmf_engine* e) {
     return 0;
 }
 
-// ---- n_features > 96: the passes run once per 96-feature block of X and W (include/salnmf.h: limits)
-// H half (update_H, _utils_klnmf.py:220-278; the H half of update_WH, :343-361) from (W, H) into Hout: U = R W^T summed
-// over the blocks' launches through Uacc, the last block's launch updates H
-static int blocked_update_H(salnmf_engine* e, double* Hout, double hfloor = kEps, bool weighted = true) {
-    for (int b = 0; b < e->NB; ++b) {
-        FusedParams p = fused_params(e);
-        to_block(e, p, b);
-        p.Hout = Hout;
-        p.hfloor = hfloor;
-        if (!weighted) p.wkl = p.wlh = nullptr;
-        p.Uacc = e->Uacc;
-        p.ublock = b == 0 ? 1 : (b == e->NB - 1 ? 3 : 2);
-        CK(weight_arrays(e, p));  // (the BLOCKED instantiation is the weighted-capable one)
-        const FusedSel sel{e->KS, e->KTM, e->KR, false, true, false, true, false, true};
-        if (launch_fused_inst(sel, p, e->grid, e->stream, nullptr, nullptr)) return fail("no kernel instantiation for KS=%d KTM=%d KR=%d", e->KS, e->KTM, e->KR);
-        HIPCK(hipGetLastError());
-    }
-    return 0;
-}
-// numerator (w_kl * X / (W H)) @ H^T of every block from (W, H) -> Gblk (compact [K][width] per block)
-static int blocked_numerators(salnmf_engine* e, bool weighted = true) {
-    for (int b = 0; b < e->NB; ++b) {
-        FusedParams p = fused_params(e);
-        to_block(e, p, b);
-        if (!weighted) p.wkl = p.wlh = nullptr;
-        CK((launch_fused<true, false, false>(e, p)));
-        TailParams t = tail_params(e, e->grid, e->Gblk + (size_t)b * e->K * VMAX, 0, 0, 0, false);
-        t.V = block_width(e, b);
-        hipLaunchKernelGGL(tail_kernel, dim3(e->K), dim3(TAIL_BLOCK), 0, e->stream, t);
-        HIPCK(hipGetLastError());
-    }
-    // sample shards: the blocks' compact numerators lie back to back (K * V doubles in all): one exchange for all of them
-    if (sharded(e)) CK(allreduce(e, e->Gblk, (size_t)e->K * e->V));
-    return 0;
-}
-// both halves in ONE pass per feature block (round 5): the block's numerator (-> Gblk, as blocked_numerators) and its share of
-// U = R W^T, accumulated over the blocks; the last block's pass writes clip(H * U) to Hout.  Every block's numerator is formed
-// from the OLD H -- only the last pass rewrites it, tile by tile behind that tile's own numerator -- so Hout may be H itself.
-// P = H W[:, block] is formed once per block instead of twice (96 x 100 000 x 3 blocks: 335 -> 215 us per joint step).
-static int blocked_joint_passes(salnmf_engine* e, double* Hout, double hfloor = kEps, bool weighted = true) {
-    for (int b = 0; b < e->NB; ++b) {
-        FusedParams p = fused_params(e);
-        to_block(e, p, b);
-        p.Hout = Hout;
-        p.hfloor = hfloor;
-        if (!weighted) p.wkl = p.wlh = nullptr;
-        p.Uacc = e->Uacc;
-        p.ublock = b == 0 ? 1 : (b == e->NB - 1 ? 3 : 2);
-        CK(weight_arrays(e, p));
-        const FusedSel sel{e->KS, e->KTM, e->KR, true, true, false, true, false, true};
-        if (launch_fused_inst(sel, p, e->grid, e->stream, nullptr, nullptr)) return fail("no kernel instantiation for KS=%d KTM=%d KR=%d", e->KS, e->KTM, e->KR);
-        HIPCK(hipGetLastError());
-        TailParams t = tail_params(e, e->grid, e->Gblk + (size_t)b * e->K * VMAX, 0, 0, 0, false);
-        t.V = block_width(e, b);
-        hipLaunchKernelGGL(tail_kernel, dim3(e->K), dim3(TAIL_BLOCK), 0, e->stream, t);
-        HIPCK(hipGetLastError());
-    }
-    if (sharded(e)) CK(allreduce(e, e->Gblk, (size_t)e->K * e->V));
-    return 0;
-}
-static int blocked_finish_W(salnmf_engine* e, int n_given, int clip_mode) {
-    hipLaunchKernelGGL(w_finish_blocked_kernel, dim3(e->K), dim3(256), 0, e->stream, e->Gblk, e->red, e->W, e->W, e->V, e->K, n_given, clip_mode);
-    HIPCK(hipGetLastError());
-    return 0;
-}
-// one joint step (update_WH, _utils_klnmf.py:281-361): both halves from the OLD (W, H), one pass per feature block
-static int blocked_kl_step_once(salnmf_engine* e, int n_given) {
-    if (n_given >= e->K) {  // W untouched (:330-331): in place
-        CK(blocked_update_H(e, e->H));
-        e->h_pending = false;
-        return 0;
-    }
-    CK(blocked_joint_passes(e, e->H));  // (both halves read the old H, a pending rescale included)
-    CK(blocked_finish_W(e, n_given, SALNMF_CLIP_ALL));
-    e->h_pending = false;  // the new H was written in full
-    return 0;
-}
-
-
-// ---- n_signatures > 64: the passes run per chunk of <= 64 signatures (include/salnmf.h: limits).  P = H W is a sum over
-// the chunks, so it is formed FIRST, by a chain of forward launches through e->PR (each adds its chunk's product; the
-// last one turns the sum into what is needed: the ratio X / P, the divergence, the per-sample divergences or P itself);
-// the update passes then run on the given ratio, once per chunk, each with the geometry of its chunk's size.
-//   W, hscale (MvNMF line-search trials): the signature matrix instead of e->W, and H read as clip(H * hscale[k]) -- both
-//   compact over all signatures
-//   b: the feature block (engines with more than 96 features AND more than 64 signatures run the chain block by block)
-static FwdParams chunk_fwd_params(salnmf_engine* e, const salnmf_engine::Chunk& c, int ci, const double* W = nullptr, const double* hscale = nullptr,
-                                  int b = 0) {
-    FwdParams p{};
-    p.X = e->X + (size_t)b * e->Np * VMAX;
-    p.H = e->H + (size_t)ci * e->Np * e->KP;
-    p.W = (W ? W : e->W) + (size_t)c.k0 * e->V + (size_t)VMAX * b;
-    p.hscale = hscale ? hscale + c.k0 : nullptr;
-    p.xlx = e->xlx ? e->xlx + (size_t)b * e->Np * 16 : nullptr;
-    p.N = e->N;
-    p.V = block_width(e, b);
-    p.ldw = e->V;
-    p.K = c.K;
-    p.ntiles = e->ntiles;
-    return p;
-}
-// the chain: chunks 0 .. NC-2 accumulate into e->PR (mode 2), the last chunk runs `last_mode` with `last` as its template
-// (out, weights) on top of the accumulated product
-static int chunk_chain(salnmf_engine* e, int last_mode, const FwdParams& last, const double* W = nullptr, const double* hscale = nullptr, int b = 0) {
-    for (int ci = 0; ci < e->NC; ++ci) {
-        const auto& c = e->kc[(size_t)ci];
-        FwdParams p = chunk_fwd_params(e, c, ci, W, hscale, b);
-        p.pin = ci == 0 ? nullptr : e->PR;
-        const bool is_last = ci == e->NC - 1;
-        if (is_last) {
-            p.wkl = last.wkl;
-            p.wlh = last.wlh;
-            p.out = last.out;
-        } else {
-            p.out = e->PR;
-        }
-        if (launch_forward_inst(c.KS, FWD_PIN + (is_last ? last_mode : 2), p, e->fgrid, e->stream, nullptr, nullptr))
-            return fail("no forward instantiation for KS=%d", c.KS);
-        HIPCK(hipGetLastError());
-    }
-    return 0;
-}
-static int chunk_ratio(salnmf_engine* e) {  // e->PR = X / (H W)
-    FwdParams last{};
-    last.out = e->PR;
-    return chunk_chain(e, 4, last);
-}
-// the update passes of every chunk on the ratio in e->PR: H half (do_u) into the chunk's columns of H, in place; W half
-// (do_g): numerator slabs, reduced and applied to the chunk's rows of W by the ordinary tail
-//   weighted = false: MvNMF's passes (no sample weights: mvnmf.py:56,162-165); g_only: the numerator rows are reduced into
-//   e->red and W is left alone (the MvNMF W step takes its own root from them)
-static int chunk_passes(salnmf_engine* e, bool do_g, bool do_u, int n_given, int clip_mode, bool weighted = true, bool g_only = false) {
-    const bool shard = sharded(e) && do_g && n_given < e->K;
-    for (int ci = 0; ci < e->NC; ++ci) {
-        const auto& c = e->kc[(size_t)ci];
-        const int given = std::max(0, std::min(c.K, n_given - c.k0));  // given rows inside this chunk
-        const bool g = do_g && given < c.K;
-        if (!g && !do_u) continue;
-        FusedParams p = fused_params(e);
-        p.X = e->PR;
-        p.H = p.Hout = e->H + (size_t)ci * e->Np * e->KP;
-        p.W = e->W + (size_t)c.k0 * e->V;
-        p.K = c.K;
-        p.hscale = nullptr;
-        if (!weighted) p.wkl = p.wlh = nullptr;
-        CK(weight_arrays(e, p));
-        FusedSel sel{c.KS, c.KTM, c.KR, g, do_u, false, true, false, false};
-        sel.RGIVEN = true;
-        if (launch_fused_inst(sel, p, e->grid, e->stream, nullptr, nullptr)) return fail("no kernel instantiation for KS=%d KTM=%d KR=%d", c.KS, c.KTM, c.KR);
-        HIPCK(hipGetLastError());
-        if (g) {
-            TailParams t = tail_params(e, e->grid, e->red + (size_t)c.k0 * e->V, given, clip_mode, (g_only || shard) ? 0 : 1, false);
-            t.W = t.Wout = e->W + (size_t)c.k0 * e->V;
-            t.K = c.K;
-            hipLaunchKernelGGL(tail_kernel, dim3(c.K), dim3(TAIL_BLOCK), 0, e->stream, t);
-            HIPCK(hipGetLastError());
-        }
-    }
-    if (shard) {
-        // the chunks' numerator rows lie in e->red as one K x V matrix: one exchange, then the W update of every row (the
-        // given rows' numerators were not formed: they are not read either)
-        CK(allreduce(e, e->red, (size_t)e->K * e->V));
-        if (!g_only) CK(launch_tail(e, 0, e->red, n_given, clip_mode, 1));
-    }
-    return 0;
-}
-// one joint step (update_WH, _utils_klnmf.py:281-361): both halves use the ratio of the OLD state, so each chunk's pass
-// updates its columns of H and its rows of W in place
-static int chunked_kl_step_once(salnmf_engine* e, int n_given) {
-    CK(chunk_ratio(e));
-    return chunk_passes(e, n_given < e->K, true, n_given, SALNMF_CLIP_ALL);
-}
-
-// ---- n_features > 96 AND n_signatures > 64 (round 5): the two decompositions together.  Per feature block b the chain over
-// the chunks forms that block's ratio R_b = X_b / (H W_b) in e->PR; on it every chunk runs its numerator pass (G of the pair
-// (chunk, block) -> its rows of the block's compact numerator in Gblk) and its share U += R_b W_(chunk, b)^T of the update_H
-// product, accumulated over the blocks through the chunk's part of Uacc; the last block's pass updates the chunk's columns of
-// H.  The chains read the OLD H of all chunks: a joint step writes the new H to the second buffer (Hout), an update_H alone
-// may go in place (the last block's chain is done before its passes).  W afterwards as on feature blocks (blocked_finish_W).
-static inline bool grid_split(const salnmf_engine* e) { return e->NB > 1 && e->NC > 1; }
-static int grid_passes(salnmf_engine* e, bool do_g, bool do_u, int n_given, double* Hout, bool weighted = true) {
-    const size_t hc = (size_t)e->Np * e->KP;
-    bool any_g = false;
-    for (int b = 0; b < e->NB; ++b) {
-        FwdParams last{};
-        last.out = e->PR;
-        CK(chunk_chain(e, 4, last, nullptr, nullptr, b));
-        const int vb = block_width(e, b);
-        for (int ci = 0; ci < e->NC; ++ci) {
-            const auto& c = e->kc[(size_t)ci];
-            const int given = std::max(0, std::min(c.K, n_given - c.k0));
-            FusedParams p = fused_params(e);
-            p.X = e->PR;
-            p.V = vb;
-            p.ldw = e->V;
-            p.W = e->W + (size_t)c.k0 * e->V + (size_t)VMAX * b;
-            p.H = p.Hout = e->H + (size_t)ci * hc;
-            p.K = c.K;
-            p.hscale = nullptr;
-            if (!weighted) p.wkl = p.wlh = nullptr;
-            CK(weight_arrays(e, p));
-            const bool g = do_g && given < c.K;
-            if (g && do_u) {  // both halves of the pair in one pass over the block's ratio
-                p.Hout = Hout + (size_t)ci * hc;
-                p.Uacc = e->Uacc + (size_t)ci * hc;
-                p.ublock = b == 0 ? 1 : (b == e->NB - 1 ? 3 : 2);
-                FusedSel sel{c.KS, c.KTM, c.KR, true, true, false, true, false, true};
-                sel.RGIVEN = true;
-                if (launch_fused_inst(sel, p, e->grid, e->stream, nullptr, nullptr)) return fail("no kernel instantiation for KS=%d KTM=%d KR=%d", c.KS, c.KTM, c.KR);
-                HIPCK(hipGetLastError());
-                TailParams t = tail_params(e, e->grid, e->Gblk + (size_t)b * e->K * VMAX + (size_t)c.k0 * vb, 0, 0, 0, false);
-                t.V = vb;
-                t.K = c.K;
-                hipLaunchKernelGGL(tail_kernel, dim3(c.K), dim3(TAIL_BLOCK), 0, e->stream, t);
-                HIPCK(hipGetLastError());
-                any_g = true;
-                continue;
-            }
-            if (g) {
-                FusedSel sel{c.KS, c.KTM, c.KR, true, false, false, true, false, false};
-                sel.RGIVEN = true;
-                if (launch_fused_inst(sel, p, e->grid, e->stream, nullptr, nullptr)) return fail("no kernel instantiation for KS=%d KTM=%d KR=%d", c.KS, c.KTM, c.KR);
-                HIPCK(hipGetLastError());
-                TailParams t = tail_params(e, e->grid, e->Gblk + (size_t)b * e->K * VMAX + (size_t)c.k0 * vb, 0, 0, 0, false);
-                t.V = vb;
-                t.K = c.K;
-                hipLaunchKernelGGL(tail_kernel, dim3(c.K), dim3(TAIL_BLOCK), 0, e->stream, t);
-                HIPCK(hipGetLastError());
-                any_g = true;
-            }
-            if (do_u) {
-                p.Hout = Hout + (size_t)ci * hc;
-                p.Uacc = e->Uacc + (size_t)ci * hc;
-                p.ublock = b == 0 ? 1 : (b == e->NB - 1 ? 3 : 2);
-                FusedSel sel{c.KS, c.KTM, c.KR, false, true, false, true, false, true};
-                sel.RGIVEN = true;
-                if (launch_fused_inst(sel, p, e->grid, e->stream, nullptr, nullptr)) return fail("no kernel instantiation for KS=%d KTM=%d KR=%d", c.KS, c.KTM, c.KR);
-                HIPCK(hipGetLastError());
-            }
-        }
-    }
-    if (any_g && sharded(e)) CK(allreduce(e, e->Gblk, (size_t)e->K * e->V));
-    if (do_u) e->h_pending = false;
-    return 0;
-}
-static int grid_kl_step_once(salnmf_engine* e, int n_given) {
-    if (n_given >= e->K) return grid_passes(e, false, true, n_given, e->H);  // W untouched (_utils_klnmf.py:330-331)
-    CK(ensure_halt(e));
-    CK(grid_passes(e, true, true, n_given, e->Halt));
-    CK(blocked_finish_W(e, n_given, SALNMF_CLIP_ALL));
-    std::swap(e->H, e->Halt);
-    return 0;
-}
+// ---- engines wider than one tile (feature blocks, signature chunks): salnmf_host_wide.h, included below
+static int wide_forward(salnmf_engine* e, int mode, const FwdParams& t, int b, const double* W = nullptr, const double* hscale = nullptr, int grid = 0);
+static int wide_passes(salnmf_engine* e, bool do_g, bool do_u, int n_given, int clip_mode, double* Hout, double hfloor = kEps, bool weighted = true,
+                       bool g_only = false);
+static int wide_kl_step_once(salnmf_engine* e, int n_given);
 
 int salnmf_set_lockstep(salnmf_engine* e, int on) {
     if (!e) return fail("null engine");
@@ -1449,18 +1201,11 @@ int salnmf_kl_step(salnmf_engine* e, int n_steps, int n_given) {
     if (!e) return fail("null engine");
     if (n_given < 0 || n_given > e->K) return fail("n_given out of range");
     CK(enter(e));
-    if (grid_split(e)) {
-        e->keep_valid = false;  // (the joint step uses the second H buffer itself)
-        for (int i = 0; i < n_steps; ++i) CK(grid_kl_step_once(e, n_given));
-        return 0;
-    }
-    if (e->NB > 1) {
-        e->keep_valid = false;  // (the joint step uses the second H buffer itself)
-        for (int i = 0; i < n_steps; ++i) CK(blocked_kl_step_once(e, n_given));
-        return 0;
-    }
-    if (e->NC > 1) {
-        for (int i = 0; i < n_steps; ++i) CK(chunked_kl_step_once(e, n_given));
+    if (split(e)) {
+        // (feature blocks have always dropped a kept state here, signature chunks alone never have: either would do -- the
+        // kept state of a split engine is a copy, salnmf_kl_step_keep -- and both are left as they were)
+        if (e->NB > 1) e->keep_valid = false;
+        for (int i = 0; i < n_steps; ++i) CK(wide_kl_step_once(e, n_given));
         return 0;
     }
     if (e->fast32 && n_steps > 0) {
@@ -1547,18 +1292,12 @@ int salnmf_kl_rollback(salnmf_engine* e) {
 int salnmf_update_H(salnmf_engine* e) {
     if (!e) return fail("null engine");
     CK(enter(e));
-    if (grid_split(e)) return grid_passes(e, false, true, 0, e->H);
-    if (e->NB > 1) {
-        CK(blocked_update_H(e, e->H));
-        e->h_pending = false;
-        return 0;
+    if (split(e)) {
+        CK(wide_passes(e, false, true, 0, 0, e->H));
+    } else {
+        FusedParams p = fused_params(e);
+        CK((launch_fused<false, true, false>(e, p)));
     }
-    if (e->NC > 1) {
-        CK(chunk_ratio(e));
-        return chunk_passes(e, false, true, 0, 0);
-    }
-    FusedParams p = fused_params(e);
-    CK((launch_fused<false, true, false>(e, p)));
     e->h_pending = false;
     return 0;
 }
@@ -1585,18 +1324,7 @@ int salnmf_update_W(salnmf_engine* e, int n_given, int clip_mode) {
     if (!e) return fail("null engine");
     CK(enter(e));
     if (n_given >= e->K) return 0;  // _utils_klnmf.py:204-205
-    if (grid_split(e)) {
-        CK(grid_passes(e, true, false, n_given, nullptr));
-        return blocked_finish_W(e, n_given, clip_mode);
-    }
-    if (e->NB > 1) {
-        CK(blocked_numerators(e));
-        return blocked_finish_W(e, n_given, clip_mode);
-    }
-    if (e->NC > 1) {
-        CK(chunk_ratio(e));
-        return chunk_passes(e, true, false, n_given, clip_mode);
-    }
+    if (split(e)) return wide_passes(e, true, false, n_given, clip_mode, nullptr);
     FusedParams p = fused_params(e);
     CK((launch_fused<true, false, false>(e, p)));
     if (sharded(e)) return sharded_tail(e, n_given, clip_mode);
@@ -1637,71 +1365,34 @@ static int objective_partials(salnmf_engine* e, const double* W, const double* h
         p.wkl = nullptr;
         p.wlh = nullptr;
     }
-    const int fgrid = grid > 0 ? grid : e->fgrid;
-    if (e->NB > 1 && e->NC > 1) {
-        // a sum over the feature blocks of the chunk chain's divergence; the l-half penalty once (the last chunk's share by
-        // block 0's last launch, the other chunks' by the small kernel)
-        int n = 0;
-        for (int b = 0; b < e->NB; ++b) {
-            FwdParams last = p;
-            if (b > 0) last.wlh = nullptr;
-            last.out = e->objpart + n;
-            CK(chunk_chain(e, 0, last, W, hscale, b));
+    const int fgrid = grid > 0 ? grid : e->fgrid;  // (e->fgrid on every split engine: wide_forward)
+    if (direct && !split(e)) {
+        p.sum_out = direct;
+        p.sum_counter = e->klcnt + 1;  // (its own word: the MvNMF update_H pass's counter is word 0)
+        CK(launch_forward<0>(e, p, fgrid, nullptr, ev));
+        *nparts = 0;
+        return 0;
+    }
+    // the KL divergence is a sum over the features: one evaluation per feature block, each with the x-only constants of its
+    // own features; the l-half penalty (klnmf.py:75-79) once -- block 0's launch adds it for the signatures it reads (all
+    // of them, or the last chunk's), the other chunks' shares come from a small kernel each
+    int n = 0;
+    for (int b = 0; b < e->NB; ++b) {
+        FwdParams t = p;
+        if (b > 0) t.wlh = nullptr;
+        t.out = e->objpart + n;
+        CK(wide_forward(e, 0, t, b, W, p.hscale, fgrid));
+        n += fgrid;
+    }
+    if (p.wlh) {
+        for (int ci = 0; ci + 1 < e->NC; ++ci) {
+            hipLaunchKernelGGL(lhalf_penalty_kernel, dim3(e->fgrid), dim3(256), 0, e->stream, e->H + (size_t)ci * e->Np * e->KP, p.wlh, e->N,
+                               e->kc[(size_t)ci].K, e->KP, e->objpart + n);
+            HIPCK(hipGetLastError());
             n += e->fgrid;
         }
-        if (p.wlh) {
-            for (int ci = 0; ci + 1 < e->NC; ++ci) {
-                hipLaunchKernelGGL(lhalf_penalty_kernel, dim3(e->fgrid), dim3(256), 0, e->stream, e->H + (size_t)ci * e->Np * e->KP, p.wlh, e->N,
-                                   e->kc[(size_t)ci].K, e->KP, e->objpart + n);
-                HIPCK(hipGetLastError());
-                n += e->fgrid;
-            }
-        }
-        *nparts = n;
-        return 0;
     }
-    if (e->NC > 1) {
-        // the chain over the signature chunks; the last launch evaluates the divergence (and its own chunk's share of the
-        // l-half penalty, klnmf.py:75-79), the other chunks' shares come from a small kernel each
-        FwdParams last = p;
-        last.out = e->objpart;
-        CK(chunk_chain(e, 0, last, W, hscale));
-        int n = e->fgrid;
-        if (p.wlh) {
-            for (int ci = 0; ci + 1 < e->NC; ++ci) {
-                hipLaunchKernelGGL(lhalf_penalty_kernel, dim3(e->fgrid), dim3(256), 0, e->stream, e->H + (size_t)ci * e->Np * e->KP, p.wlh, e->N,
-                                   e->kc[(size_t)ci].K, e->KP, e->objpart + n);
-                HIPCK(hipGetLastError());
-                n += e->fgrid;
-            }
-        }
-        *nparts = n;
-        return 0;
-    }
-    if (e->NB > 1) {
-        // the KL divergence is a sum over the features: one forward pass per feature block, each with the x-only
-        // constants of its own features; the l-half penalty (klnmf.py:75-79) once
-        for (int b = 0; b < e->NB; ++b) {
-            FwdParams pb = p;
-            pb.X = e->X + (size_t)b * e->Np * VMAX;
-            pb.W = W + (size_t)VMAX * b;
-            pb.V = block_width(e, b);
-            pb.xlx = e->xlx + (size_t)b * e->Np * 16;
-            if (b > 0) pb.wlh = nullptr;
-            pb.out = e->objpart + (size_t)b * fgrid;
-            CK(launch_forward<0>(e, pb, fgrid));
-        }
-    } else {
-        if (direct) {
-            p.sum_out = direct;
-            p.sum_counter = e->klcnt + 1;  // (its own word: the MvNMF update_H pass's counter is word 0)
-            CK(launch_forward<0>(e, p, fgrid, nullptr, ev));
-            *nparts = 0;
-            return 0;
-        }
-        CK(launch_forward<0>(e, p, fgrid));
-    }
-    *nparts = e->NB * fgrid;
+    *nparts = n;
     return 0;
 }
 
@@ -1831,42 +1522,18 @@ int salnmf_samplewise_kl(salnmf_engine* e, double* out) {
     FwdParams p;
     CK(fwd_params(e, p));
     HIPCK(hipMalloc(&dev, (size_t)e->NB * e->Np * sizeof(double)));
-    if (e->NC > 1) {
-        int rcc = 0;
-        for (int b = 0; b < e->NB && !rcc; ++b) {  // (feature blocks as well: a sum over the blocks, as below)
-            FwdParams last{};
-            last.out = dev + (size_t)b * e->Np;
-            rcc = chunk_chain(e, 1, last, nullptr, nullptr, b);
-        }
-        if (!rcc) rcc = download(e, out, dev, (size_t)e->N);
-        std::vector<double> part(e->NB > 1 ? (size_t)e->N : 0);
-        for (int b = 1; b < e->NB && !rcc; ++b) {
-            rcc = download(e, part.data(), dev + (size_t)b * e->Np, (size_t)e->N);
-            if (!rcc)
-                for (int64_t n = 0; n < e->N; ++n) out[n] += part[(size_t)n];
-        }
-        (void)hipFree(dev);
-        return rcc;
-    }
     int rc = 0;
-    for (int b = 0; b < e->NB && !rc; ++b) {  // (per-sample divergences are sums over the features: one pass per feature block)
-        FwdParams pb = p;
-        if (e->NB > 1) {
-            pb.X = e->X + (size_t)b * e->Np * VMAX;
-            pb.W = e->W + (size_t)VMAX * b;
-            pb.V = block_width(e, b);
-        }
-        pb.out = dev + (size_t)b * e->Np;
-        rc = launch_forward<1>(e, pb);
+    for (int b = 0; b < e->NB && !rc; ++b) {  // (per-sample divergences are sums over the features: one evaluation per feature block)
+        FwdParams t = p;
+        t.out = dev + (size_t)b * e->Np;
+        rc = wide_forward(e, 1, t, b, nullptr, p.hscale);
     }
     if (!rc) rc = download(e, out, dev, (size_t)e->N);
-    if (!rc && e->NB > 1) {
-        std::vector<double> part((size_t)e->N);
-        for (int b = 1; b < e->NB && !rc; ++b) {
-            rc = download(e, part.data(), dev + (size_t)b * e->Np, (size_t)e->N);
-            if (!rc)
-                for (int64_t n = 0; n < e->N; ++n) out[n] += part[(size_t)n];
-        }
+    std::vector<double> part(e->NB > 1 ? (size_t)e->N : 0);
+    for (int b = 1; b < e->NB && !rc; ++b) {
+        rc = download(e, part.data(), dev + (size_t)b * e->Np, (size_t)e->N);
+        if (!rc)
+            for (int64_t n = 0; n < e->N; ++n) out[n] += part[(size_t)n];
     }
     (void)hipFree(dev);
     return rc;
@@ -1881,44 +1548,22 @@ int salnmf_reconstruct(salnmf_engine* e, double* out) {
     HIPCK(hipMalloc(&dev, (size_t)e->Np * VMAX * sizeof(double)));
     p.out = dev;
     int rc = 0;
-    if (e->NC > 1 && e->NB > 1) {
-        std::vector<double> part((size_t)e->N * VMAX);
-        for (int b = 0; b < e->NB && !rc; ++b) {  // the chunk chain of one feature block at a time
-            FwdParams last{};
-            last.out = dev;
-            const int vb = block_width(e, b);
-            rc = chunk_chain(e, 2, last, nullptr, nullptr, b);
-            if (!rc) rc = download_padded(e, part.data(), dev, vb, VMAX);
-            if (!rc)
-                for (int64_t n = 0; n < e->N; ++n)
-                    memcpy(out + (size_t)n * e->V + (size_t)VMAX * b, part.data() + (size_t)n * vb, (size_t)vb * sizeof(double));
-        }
-    } else if (e->NC > 1) {
-        FwdParams last{};
-        last.out = dev;
-        rc = chunk_chain(e, 2, last);
-        if (!rc) rc = download_padded(e, out, dev, e->V, VMAX);
-    } else if (e->NB == 1) {
-        rc = launch_forward<2>(e, p);
-        if (!rc) rc = download_padded(e, out, dev, e->V, VMAX);
-    } else {
-        // one feature block at a time: H @ W[:, block] into the scratch image, its columns into the caller's rows
-        std::vector<double> part((size_t)e->N * VMAX);
-        for (int b = 0; b < e->NB && !rc; ++b) {
-            FwdParams pb = p;
-            pb.W = e->W + (size_t)VMAX * b;
-            pb.V = block_width(e, b);
-            rc = launch_forward<2>(e, pb);
-            if (!rc) rc = download_padded(e, part.data(), dev, pb.V, VMAX);
-            if (!rc)
-                for (int64_t n = 0; n < e->N; ++n)
-                    memcpy(out + (size_t)n * e->V + (size_t)VMAX * b, part.data() + (size_t)n * pb.V, (size_t)pb.V * sizeof(double));
-        }
+    // one feature block at a time: H @ W[:, block] into the scratch image, its columns into the caller's rows (one block:
+    // straight into them)
+    std::vector<double> part(e->NB > 1 ? (size_t)e->N * VMAX : 0);
+    for (int b = 0; b < e->NB && !rc; ++b) {
+        const int vb = block_width(e, b);
+        rc = wide_forward(e, 2, p, b, nullptr, p.hscale);
+        if (!rc) rc = download_padded(e, e->NB > 1 ? part.data() : out, dev, vb, VMAX);
+        if (!rc && e->NB > 1)
+            for (int64_t n = 0; n < e->N; ++n)
+                memcpy(out + (size_t)n * e->V + (size_t)VMAX * b, part.data() + (size_t)n * vb, (size_t)vb * sizeof(double));
     }
     (void)hipFree(dev);
     return rc;
 }
 
+#include "salnmf_host_wide.h"  // feature blocks and signature chunks: the forward evaluation and the update-pass driver
 #include "salnmf_host_mv.h"  // MvNMF entry points and their host-side logic
 #include "salnmf_host_corr.h"  // CorrNMF / MultimodalCorrNMF entry points
 #include "salnmf_host_init.h"  // device-side initialisation entry points

@@ -114,10 +114,10 @@ int salnmf_corr_compute_exposures(salnmf_engine* e) {
 
 int salnmf_corr_compute_aux(salnmf_engine* e) {
     CK(corr_ready(e));
-    if (e->NB > 1) {
+    if (split(e)) {
         // U = R W^T summed over the feature blocks, aux = H * U unclipped by the last block's launch; the numerators of
         // update_signatures block by block into Gblk (applied by salnmf_corr_update_signatures)
-        return blocked_joint_passes(e, e->aux, 0.0, false);  // (one pass per block for both)
+        return wide_passes(e, true, true, 0, 0, e->aux, 0.0, false, true);  // (one pass per block for both)
     }
     FusedParams p = fused_params(e);
     p.wkl = nullptr;  // CorrNMF is unweighted (corrnmf_det.py:80-85)
@@ -134,8 +134,7 @@ int salnmf_corr_update_signatures(salnmf_engine* e, int n_given) {
     CK(corr_ready(e));
     if (n_given < 0 || n_given > e->K) return fail("n_given out of range");
     if (n_given >= e->K) return 0;  // _utils_klnmf.py:204-205
-    if (e->NB > 1) return blocked_finish_W(e, n_given, SALNMF_CLIP_NON_GIVEN);
-    return launch_tail(e, 0, e->red, n_given, SALNMF_CLIP_NON_GIVEN, 1);
+    return wide_apply_W(e, n_given, SALNMF_CLIP_NON_GIVEN);  // (one block: the plain tail on the reduced numerators)
 }
 
 int salnmf_corr_update_signature_scalings(salnmf_engine* e) {

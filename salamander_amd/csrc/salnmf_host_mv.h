@@ -14,8 +14,6 @@ static int mv_logdet_to_slot(salnmf_engine* e, const double* W, double delta, in
 // numerator passes, the W-only algebra, root, and a host-driven line search whose objectives are the KLNMF path's forward
 // passes.  No speculation: such a problem spends its time in the passes over the samples
 // (csrc/salnmf_mv_wide_kernels.h has the kernels).
-static inline bool mv_wide(const salnmf_engine* e) { return split(e); }
-static int mv_wide_check(const salnmf_engine*) { return 0; }  // (round 5: every split engine runs MvNMF, sample shards included)
 // (signature chunks) the K x 2K scratch of the global-memory elimination
 static int ensure_mv_scratch(salnmf_engine* e) {
     if (e->mvS) return 0;
@@ -38,16 +36,8 @@ static int mv_wide_logdet(salnmf_engine* e, const double* W, double delta, int s
 }
 // update_H of an MvNMF step (MvNMF._update_H, mvnmf.py:162-165: in place, unweighted) on a split engine
 static int mv_wide_update_H(salnmf_engine* e) {
-    if (grid_split(e)) {
-        CK(flush_H_scale(e));
-        return grid_passes(e, false, true, 0, e->H, false);
-    }
-    if (e->NC > 1) {
-        CK(flush_H_scale(e));
-        CK(chunk_ratio(e));
-        return chunk_passes(e, false, true, 0, 0, false);
-    }
-    CK(blocked_update_H(e, e->H, kEps, false));
+    // (feature blocks alone: the passes apply a pending rescale on the fly; with signature chunks none is ever pending)
+    CK(wide_passes(e, false, true, 0, 0, e->H, kEps, false));
     e->h_pending = false;
     return 0;
 }
@@ -62,18 +52,14 @@ static int rowsums_H_block(salnmf_engine* e, const double* H, int Kc, double* ou
     HIPCK(hipGetLastError());
     return 0;
 }
-// numerator of (W, H) -> Gblk (feature blocks) / red (signature chunks), rowsums_H -> red + K V, A = W Y_minus, B = W |Y|
+// numerator of (W, H) -> wide_numerators(e), rowsums_H -> red + K V, A = W Y_minus, B = W |Y|
 // -> mvA, mvB, log det(W) -> scal[3]
 static int mv_wide_prepare(salnmf_engine* e, double delta) {
     CK(flush_H_scale(e));  // (the column sums below read H as it is)
+    if (e->NC > 1) CK(ensure_mv_scratch(e));
+    // every numerator, W untouched; update_W_unconstrained takes no weights (mvnmf.py:37-66): as the narrow path
+    CK(wide_passes(e, true, false, 0, 0, nullptr, kEps, false, true));
     if (e->NC > 1) {
-        CK(ensure_mv_scratch(e));
-        if (grid_split(e)) {
-            CK(grid_passes(e, true, false, 0, nullptr, false));  // every (chunk, block) pair's numerator -> Gblk
-        } else {
-            CK(chunk_ratio(e));
-            CK(chunk_passes(e, true, false, 0, 0, false, true));  // every row's numerator, W untouched
-        }
         for (int ci = 0; ci < e->NC; ++ci) {
             const auto& c = e->kc[(size_t)ci];
             CK(rowsums_H_block(e, e->H + (size_t)ci * e->Np * e->KP, c.K, e->red + (size_t)e->K * e->V + c.k0));
@@ -87,7 +73,6 @@ static int mv_wide_prepare(salnmf_engine* e, double delta) {
         HIPCK(hipGetLastError());
         return 0;
     }
-    CK(blocked_numerators(e, false));  // update_W_unconstrained takes no weights (mvnmf.py:37-66): as the narrow path
     CK(rowsums_H_block(e, e->H, e->K, e->red + (size_t)e->K * e->V));
     if (sharded(e)) CK(allreduce(e, e->red + (size_t)e->K * e->V, (size_t)e->K));  // rowsums_H over all shards
     hipLaunchKernelGGL(mv_prepare_W_wide_kernel, dim3(1), dim3(MV_BLOCK), 0, e->stream, e->W, e->K, e->V, delta, e->mvA, e->mvB, e->scal + 3);
@@ -96,7 +81,7 @@ static int mv_wide_prepare(salnmf_engine* e, double delta) {
 }
 static int mv_wide_root(salnmf_engine* e, double lam, int n_given) {
     hipLaunchKernelGGL(mv_trial_row_wide_kernel<true>, dim3(e->K), dim3(256), 0, e->stream, e->W, e->Wunc, 1.0, 0, e->K, e->V, e->Wtrial, e->cs, e->mvA,
-                       e->mvB, (e->NC > 1 && e->NB == 1) ? e->red : e->Gblk, e->red + (size_t)e->K * e->V, lam, n_given);
+                       e->mvB, wide_numerators(e), e->red + (size_t)e->K * e->V, lam, n_given);
     HIPCK(hipGetLastError());
     return 0;
 }
@@ -141,11 +126,10 @@ static int mv_wide_update_W(salnmf_engine* e, int n_given, double lam, double de
 }
 
 int salnmf_mv_objective(salnmf_engine* e, double lam, double delta, double* out) {
-    if (e && split(e)) CK(mv_wide_check(e));
     if (!e || !out) return fail("null argument");
     CK(enter(e));
     CK(objective_to_slot(e, e->W, nullptr, false, 0));
-    if (mv_wide(e))
+    if (split(e))
         CK(mv_wide_logdet(e, e->W, delta, 3));
     else
         CK(mv_logdet_to_slot(e, e->W, delta, 3));
@@ -636,19 +620,17 @@ static int mv_steps_queued(salnmf_engine* e, int n_steps, int n_given, double la
 }
 
 int salnmf_mv_update_W(salnmf_engine* e, int n_given, double lam, double delta, double* gamma_inout) {
-    if (e && split(e)) CK(mv_wide_check(e));
     if (!e || !gamma_inout) return fail("null argument");
     e->keep_valid = false;  // (the MvNMF steps use the second H buffer themselves)
     CK(enter(e));
-    if (mv_wide(e)) return mv_wide_update_W(e, n_given, lam, delta, gamma_inout, nullptr);
+    if (split(e)) return mv_wide_update_W(e, n_given, lam, delta, gamma_inout, nullptr);
     return mv_update_W_impl(e, n_given, lam, delta, gamma_inout, false, false);
 }
 
 int salnmf_mv_logdet(salnmf_engine* e, double delta, double* out) {
-    if (e && split(e)) CK(mv_wide_check(e));
     if (!e || !out) return fail("null argument");
     CK(enter(e));
-    if (mv_wide(e))
+    if (split(e))
         CK(mv_wide_logdet(e, e->W, delta, 3));
     else
         CK(mv_logdet_to_slot(e, e->W, delta, 3));
@@ -656,12 +638,11 @@ int salnmf_mv_logdet(salnmf_engine* e, double delta, double* out) {
 }
 
 int salnmf_mv_update_W_unconstrained(salnmf_engine* e, int n_given, double lam, double delta, double* Wunc_out) {
-    if (e && split(e)) CK(mv_wide_check(e));
     if (!e || !Wunc_out) return fail("null argument");
     if (n_given < 0 || n_given > e->K) return fail("n_given out of range");
     CK(enter(e));
     if (n_given >= e->K) return download(e, Wunc_out, e->W, (size_t)e->K * e->V);  // every column given: W itself (mvnmf.py:61)
-    if (mv_wide(e)) {
+    if (split(e)) {
         CK(mv_wide_prepare(e, delta));
         CK(mv_wide_root(e, lam, n_given));
         return download(e, Wunc_out, e->Wunc, (size_t)e->K * e->V);  // (W, H untouched; the trial buffers are scratch)
@@ -671,11 +652,10 @@ int salnmf_mv_update_W_unconstrained(salnmf_engine* e, int n_given, double lam, 
 }
 
 int salnmf_mv_line_search(salnmf_engine* e, double lam, double delta, double* gamma_inout, const double* Wunc) {
-    if (e && split(e)) CK(mv_wide_check(e));
     if (!e || !gamma_inout || !Wunc) return fail("null argument");
     e->keep_valid = false;
     CK(enter(e));
-    if (mv_wide(e)) {
+    if (split(e)) {
         HIPCK(hipMemcpyAsync(e->Wunc, Wunc, (size_t)e->K * e->V * sizeof(double), hipMemcpyHostToDevice, e->stream));
         HIPCK(hipStreamSynchronize(e->stream));  // (the caller's array is free again)
         return mv_wide_line_search(e, lam, delta, gamma_inout, false, false, nullptr);
@@ -689,12 +669,11 @@ int salnmf_mv_step(salnmf_engine* e, int n_steps, int n_given, double lam, doubl
 
 int salnmf_mv_step_objective(salnmf_engine* e, int n_steps, int n_given, double lam, double delta, double* gamma_inout, double* objective_out,
                              int more_follows) {
-    if (e && split(e)) CK(mv_wide_check(e));
     if (!e || !gamma_inout) return fail("null argument");
     if (n_steps < 1 && objective_out) return fail("n_steps must be positive");
     if (n_given < 0 || n_given > e->K) return fail("n_given out of range");
     HIPCK(hipSetDevice(e->device));
-    if (mv_wide(e)) {
+    if (split(e)) {
         CK(enter(e));
         e->keep_valid = false;
         double f = 0.0;
