@@ -629,6 +629,39 @@ int salnmf_assign_signatures_ex(int device, const double* counts, int64_t n_samp
                                 double* exposures_quantiles, double* exposures_mean, double* exposures_resampled,
                                 int* readd_round, double* kl_decrease, double* timings);
 
+/* ---- Goodness of fit of a sample to a catalogue by parametric bootstrap (csrc/salnmf_gof.h).
+ * A model draw: row n of draw b is one multinomial draw of totals[n] trials from the spectrum of exposures h = exposures[n, :]
+ * under the signatures W (rows of sum one; n_signatures <= 96, n_features <= 96):
+ *   P_v = sum_k h_k W[k, v], from 0.0 in ascending k, every term a rounded product followed by a rounded sum (no fused
+ *   multiply-add);  S = sum_v P_v, from 0.0 in ascending v.  With S == 0, S not finite or totals[n] == 0 the row is zero;
+ *   m_v = (uint64) floor((P_v / S) 2^40) (IEEE division, truncating conversion), cum_v their 64-bit prefix sums, M = cum_{V-1};
+ *   generator: Philox4x32-10, key = (seed & 0xffffffff, seed >> 32);
+ *   block q of row n of draw b: counter (q, 0x474F4644, n, b) -> words (o0, o1, o2, o3) -- the resampler's second counter word
+ *   is 0 and the split's 0x53504C54, so the three streams never meet under one seed;
+ *   draw 2q uses u = o0 | o1 << 32, draw 2q + 1 uses u = o2 | o3 << 32; draws j >= totals[n] are discarded;
+ *   t = floor(u M / 2^64), and the draw lands in the smallest v with cum_v > t.
+ * Integer arithmetic after the weights: the same bits on every run, cells of weight 0 stay 0, draw b does not depend on
+ * n_draws.  Refused before any launch: exposures or signatures that are not finite or are negative, totals that are not
+ * integers in [0, 2^32), n_draws outside [1, 65536].  out: n_draws x n_samples x n_features, plain counts. */
+int salnmf_draw_model_counts(int device, const double* exposures, int64_t n_samples, int n_signatures, const double* signatures,
+                             int n_features, const double* totals, int n_draws, uint64_t seed, double* out);
+/* The test: the observed counts are refitted exactly as salnmf_refit_exposures refits them (exposures, errors, n_iterations,
+ * converged: the same bits); draw b is salnmf_draw_model_counts of those exposures -- read where the refit left them on the
+ * device -- with the rows' own totals, written device to device as max(count, SALNMF_EPSILON) in chunks whose buffer stays
+ * within chunk_bytes (<= 0: 256 MiB; at least one draw per chunk; the results do not depend on it), and refitted in the same
+ * way: null_errors and null_n_iterations, n_draws x n_samples, are bit for bit what salnmf_refit_exposures returns for the
+ * draw.  Reduction, one thread per sample in ascending b: n_exceed[n] counts the draws with null_errors[b, n] >= errors[n]
+ * (false for a NaN on either side); null_mean[n] is the sum of null_errors[b, n] from 0.0, divided by n_draws.  The p-value is
+ * (1 + n_exceed) / (n_draws + 1).  draws: NULL, or n_draws x n_samples x n_features, plain counts.  The counts must be what
+ * salnmf_resample_counts accepts, n_draws in [1, 65536].  timings: NULL, or 4 doubles -- milliseconds by device events of the
+ * draw launches, the refit launches and the reduction, and the number of chunks.
+ * Everything is validated on the host before any launch; status 1 and salnmf_last_error otherwise. */
+int salnmf_goodness_of_fit(int device, const double* counts, int64_t n_samples, int n_features, const double* signatures,
+                           int n_signatures, int n_draws, uint64_t seed, int min_iterations, int max_iterations, int conv_test_freq,
+                           double tol, int64_t chunk_bytes, double* exposures, double* errors, int* n_iterations, int* converged,
+                           int* n_exceed, double* null_mean, double* null_errors, int* null_n_iterations, double* draws,
+                           double* timings);
+
 #ifdef __cplusplus
 }
 #endif

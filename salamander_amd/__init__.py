@@ -11,6 +11,7 @@ from ._lib import EngineUnavailable
 from .anndata_compat import AnnData, MuData
 from .assign import AssignResult, assign_signatures
 from .engine import Engine
+from .gof import GofResult, draw_model_counts, goodness_of_fit
 from .refit import RefitResult, refit_exposures
 from .resample import resample_counts
 from .split import split_counts
@@ -18,4 +19,4 @@ from .stability import signature_stability
 
 __version__ = "0.1.0"
 __all__ = ["models", "Engine", "AnnData", "MuData", "EngineUnavailable", "resample_counts", "signature_stability", "refit_exposures", "RefitResult", "assign_signatures",
-           "AssignResult", "split_counts"]
+           "AssignResult", "split_counts", "goodness_of_fit", "draw_model_counts", "GofResult"]

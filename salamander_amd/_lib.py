@@ -139,6 +139,10 @@ SIGNATURES = {
     "salnmf_assign_signatures_ex": (c_int, [c_int, _D, c_int64, c_int, _D, c_int, c_int, c_uint64, c_int, _D, c_int, c_int, c_int, c_double, c_double, c_int64,
                                             POINTER(c_uint8), POINTER(c_uint8), c_int,
                                             _D, _I, _D, _I, _D, _I, POINTER(c_int64), _I, _D, _D, _I, _I, _D, _D, _D, _D, _I, _D, _D]),
+    # goodness of fit by parametric bootstrap: salamander_amd/gof.py
+    "salnmf_draw_model_counts": (c_int, [c_int, _D, c_int64, c_int, _D, c_int, _D, c_int, c_uint64, _D]),
+    "salnmf_goodness_of_fit": (c_int, [c_int, _D, c_int64, c_int, _D, c_int, c_int, c_uint64, c_int, c_int, c_int, c_double, c_int64,
+                                       _D, _D, _I, _I, _I, _D, _D, _I, _D, _D]),
 }
 
 OBJECTIVE_SLOTS = 256  # SALNMF_OBJECTIVE_SLOTS

@@ -11,6 +11,8 @@
 #include "salnmf_refit.h"
 #include "salnmf_resample.h"
 #include "salnmf_split.h"
+#define SALNMF_GOF_KERNELS 1
+#include "salnmf_gof.h"
 #include "salnmf_stability.h"
 
 #include <algorithm>
@@ -299,6 +301,21 @@ int salnmf::refit_check_counts(const double* X, int64_t N, int V, std::vector<ui
 void salnmf::refit_launch_resample(const uint32_t* counts, double* out, int64_t N, int V, uint64_t seed, int first, int count, hipStream_t stream) {
     // compact rows, no pad rows, entries max(count, EPSILON): the clip fit() applies to X
     launch_resample(ResampleArgs{counts, out, N, N, V, V, (uint32_t)seed, (uint32_t)(seed >> 32), SALNMF_EPSILON, (uint32_t)first}, count, stream);
+}
+
+// ---- the model draw and the exceedance count as salnmf_refit.hip uses them (salnmf_gof.h): philox4x32_10 comes from
+// salnmf_resample.h, which this translation unit alone includes
+void salnmf::gof_launch_model_draw(const double* H, const double* W, const uint32_t* totals, const double* X, double* out, int64_t N, int V, int K,
+                                   uint64_t seed, double floor, int first, int count, hipStream_t stream) {
+    for (int done = 0; done < count; done += GOF_GRID_Y) {
+        const int now = std::min(GOF_GRID_Y, count - done);
+        const ModelDrawArgs a{H, W, totals, X, out + (size_t)done * N * V, N, V, K, (uint32_t)seed, (uint32_t)(seed >> 32), floor, (uint32_t)(first + done)};
+        hipLaunchKernelGGL(model_draw_kernel, dim3((unsigned)N, (unsigned)now), dim3(RESAMPLE_BLOCK), 0, stream, a);
+    }
+}
+
+void salnmf::gof_launch_reduce(const GofReduceArgs& a, hipStream_t stream) {
+    hipLaunchKernelGGL(gof_reduce_kernel, dim3((unsigned)((a.N + 255) / 256)), dim3(256), 0, stream, a);
 }
 
 // ---- signature stability (salnmf_stability.h): the two feeders share everything after their own validation

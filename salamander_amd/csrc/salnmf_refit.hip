@@ -1,7 +1,8 @@
 // Host side of the refit to fixed signatures (include/salnmf.h: salnmf_refit_exposures) and its two kernels
 // (salnmf_refit.h: refit_kernel, refit_reduce_kernel); and of the sparse assignment built on it
 // (salnmf_assign_signatures, salnmf_assign_signatures_ex; salnmf_assign.h: assign_kernel, assign_selection_kernel), DESIGN.md sections 14
-// and 14.1.
+// and 14.1; and of the goodness-of-fit test built on it (salnmf_draw_model_counts, salnmf_goodness_of_fit; salnmf_gof.h:
+// model_draw_kernel, gof_reduce_kernel, which salnmf_batch.hip compiles), DESIGN.md section 16.
 #define SALNMF_TEMPLATES_ONLY 1
 #define SALNMF_REFIT_KERNELS 1
 #include "../../include/salnmf.h"
@@ -9,6 +10,7 @@
 #include "salnmf_device.h"
 #include "salnmf_refit.h"
 #include "salnmf_assign.h"
+#include "salnmf_gof.h"
 
 #include <algorithm>
 #include <cmath>
@@ -434,6 +436,162 @@ extern "C" int salnmf_assign_signatures_ex(int device, const double* counts, int
     HIPCK(hipMemcpyAsync(dense_n_iterations, dnit_d, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, d.stream));
     HIPCK(hipMemcpyAsync(dense_converged, dconv_d, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, d.stream));
     HIPCK(hipStreamSynchronize(d.stream));
+    if (timings) {
+        for (int i = 0; i < 3; ++i) {
+            double total = 0.0;
+            for (const auto& pr : spans[i]) {
+                float ms = 0.f;
+                HIPCK(hipEventElapsedTime(&ms, pr.first, pr.second));
+                total += (double)ms;
+            }
+            timings[i] = total;
+        }
+        timings[3] = (double)n_chunks;
+    }
+    return 0;
+}
+
+// ---- goodness of fit by parametric bootstrap (salnmf_gof.h)
+
+static int gof_check_draws(int n_draws) {
+    if (n_draws < 1 || n_draws > GOF_MAX_DRAWS) return fail("n_draws must be in [1, %d], got %d", GOF_MAX_DRAWS, n_draws);
+    return 0;
+}
+
+extern "C" int salnmf_draw_model_counts(int device, const double* exposures, int64_t n_samples, int n_signatures, const double* signatures,
+                                        int n_features, const double* totals, int n_draws, uint64_t seed, double* out) {
+    const int64_t N = n_samples;
+    const int V = n_features, K = n_signatures, B = n_draws;
+    if (!exposures || !signatures || !totals || !out) return fail("null argument");
+    if (N < 1 || N > 0x7fffffff) return fail("n_samples must be in [1, 2^31), got %lld", (long long)N);
+    if (V < 1 || V > GOF_VMAX) return fail("n_features must be in [1, %d], got %d", GOF_VMAX, V);
+    if (K < 1 || K > GOF_KMAX) return fail("n_signatures must be in [1, %d], got %d", GOF_KMAX, K);
+    CK(gof_check_draws(B));
+    for (size_t i = 0; i < (size_t)N * K; ++i)
+        if (!std::isfinite(exposures[i]) || exposures[i] < 0.0)
+            return fail("exposures must be finite and not negative: row %lld, signature %d holds %g", (long long)(i / K), (int)(i % K), exposures[i]);
+    for (size_t i = 0; i < (size_t)K * V; ++i)
+        if (!std::isfinite(signatures[i]) || signatures[i] < 0.0)
+            return fail("signature %d, feature %d: entries must be finite and not negative, got %g", (int)(i / V), (int)(i % V), signatures[i]);
+    std::vector<uint32_t> trials((size_t)N);
+    for (int64_t n = 0; n < N; ++n) {
+        const double t = totals[n];
+        if (!(t >= 0.0) || t >= 4294967296.0 || t != (double)(uint64_t)t)
+            return fail("totals must be non-negative integers below 2^32: row %lld holds %g", (long long)n, t);
+        trials[(size_t)n] = (uint32_t)t;
+    }
+    hipDeviceProp_t prop;
+    CK(open_device(device, &prop));
+    const size_t NV = (size_t)N * V;
+    const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(B, ((int64_t)256 << 20) / (int64_t)(sizeof(double) * NV)));
+    DevBufs d;
+    CK(d.own_stream());
+    double* dH = d.get<double>((size_t)N * K);
+    double* dW = d.get<double>((size_t)K * V);
+    uint32_t* dT = d.get<uint32_t>((size_t)N);
+    double* dout = d.get<double>((size_t)chunk * NV);
+    if (!dH || !dW || !dT || !dout) return fail("hipMalloc failed (%d draws of %lld x %d)", chunk, (long long)N, V);
+    HIPCK(hipMemcpyAsync(dH, exposures, (size_t)N * K * sizeof(double), hipMemcpyHostToDevice, d.stream));
+    HIPCK(hipMemcpyAsync(dW, signatures, (size_t)K * V * sizeof(double), hipMemcpyHostToDevice, d.stream));
+    HIPCK(hipMemcpyAsync(dT, trials.data(), trials.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+    for (int first = 0; first < B; first += chunk) {
+        const int count = std::min(chunk, B - first);
+        gof_launch_model_draw(dH, dW, dT, nullptr, dout, N, V, K, seed, 0.0, first, count, d.stream);
+        HIPCK(hipGetLastError());
+        HIPCK(hipMemcpyAsync(out + (size_t)first * NV, dout, (size_t)count * NV * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    }
+    HIPCK(hipStreamSynchronize(d.stream));
+    return 0;
+}
+
+extern "C" int salnmf_goodness_of_fit(int device, const double* counts, int64_t n_samples, int n_features, const double* signatures, int n_signatures,
+                                      int n_draws, uint64_t seed, int min_iterations, int max_iterations, int conv_test_freq, double tol,
+                                      int64_t chunk_bytes, double* exposures, double* errors, int* n_iterations, int* converged, int* n_exceed,
+                                      double* null_mean, double* null_errors, int* null_n_iterations, double* draws, double* timings) {
+    const int64_t N = n_samples;
+    const int V = n_features, K = n_signatures, B = n_draws;
+    if (!counts || !signatures || !exposures || !errors || !n_iterations || !converged || !n_exceed || !null_mean || !null_errors || !null_n_iterations)
+        return fail("null argument");
+    CK(gof_check_draws(B));
+    RefitInputs in;
+    CK(refit_prepare(device, counts, N, V, signatures, K, 0, 0, nullptr, min_iterations, max_iterations, conv_test_freq, tol, true, in));
+    CK(refit_check_counts(counts, N, V, in.icounts));  // integer counts, row totals below 2^32 (the values themselves are not used)
+    const int cus = in.cus;
+    const size_t NV = (size_t)N * V, NK = (size_t)N * K, NB = (size_t)N * B;
+
+    // draws per chunk: the [chunk][N][V] buffer stays within chunk_bytes (at least one draw)
+    const int64_t budget = chunk_bytes > 0 ? chunk_bytes : (int64_t)256 << 20;
+    const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(B, budget / (int64_t)(sizeof(double) * NV)));
+
+    DevBufs d;
+    CK(d.own_stream());
+    double* dW = d.get<double>((size_t)K * V);
+    double* dX = d.get<double>(NV);
+    double* dH = d.get<double>(NK);
+    double* derr = d.get<double>((size_t)N);
+    int* dnit = d.get<int>((size_t)N);
+    int* dconv = d.get<int>((size_t)N);
+    unsigned* dnext = d.get<unsigned>(1);
+    double* dXb = d.get<double>((size_t)chunk * NV);
+    double* dHb = d.get<double>((size_t)chunk * NK);
+    double* derr_b = d.get<double>(NB);
+    int* dnit_b = d.get<int>(NB);
+    int* dconv_b = d.get<int>((size_t)chunk * N);
+    int* dexceed = d.get<int>((size_t)N);
+    double* dmean = d.get<double>((size_t)N);
+    if (!dW || !dX || !dH || !derr || !dnit || !dconv || !dnext || !dXb || !dHb || !derr_b || !dnit_b || !dconv_b || !dexceed || !dmean)
+        return fail("hipMalloc failed (%d draws of %lld x %d, %d signatures)", B, (long long)N, V, K);
+    HIPCK(hipMemcpyAsync(dW, signatures, (size_t)K * V * sizeof(double), hipMemcpyHostToDevice, d.stream));
+    HIPCK(hipMemcpyAsync(dX, in.x.data(), NV * sizeof(double), hipMemcpyHostToDevice, d.stream));
+
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> spans[3];  // draw, refit, reduce
+    auto timed = [&](int which, auto&& body) -> int {
+        hipEvent_t e0 = timings ? d.mark() : nullptr;
+        CK(body());
+        hipEvent_t e1 = timings ? d.mark() : nullptr;
+        if (timings && (!e0 || !e1)) return fail("event record failed");
+        if (timings) spans[which].emplace_back(e0, e1);
+        return 0;
+    };
+    const RefitArgs a{dX, dW, dH, derr, dnit, dconv, dnext, N, V, K, min_iterations, max_iterations, conv_test_freq, tol};
+    CK(timed(1, [&] { return launch_refit(a, cus, d.stream); }));
+    int n_chunks = 0;
+    for (int first = 0; first < B; first += chunk, ++n_chunks) {
+        const int count = std::min(chunk, B - first);
+        // from the device-resident exposures of the observed refit; a row's trial count is read off the clipped counts
+        CK(timed(0, [&]() -> int {
+            gof_launch_model_draw(dH, dW, nullptr, dX, dXb, N, V, K, seed, SALNMF_EPSILON, first, count, d.stream);
+            HIPCK(hipGetLastError());
+            return 0;
+        }));
+        if (draws) HIPCK(hipMemcpyAsync(draws + (size_t)first * NV, dXb, (size_t)count * NV * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+        RefitArgs c = a;
+        c.X = dXb;
+        c.P = (int64_t)count * N;
+        c.H = dHb;
+        c.err = derr_b + (size_t)first * N;
+        c.nit = dnit_b + (size_t)first * N;
+        c.conv = dconv_b;
+        CK(timed(1, [&] { return launch_refit(c, cus, d.stream); }));
+    }
+    const GofReduceArgs red{derr, derr_b, dexceed, dmean, N, B};
+    CK(timed(2, [&]() -> int {
+        gof_launch_reduce(red, d.stream);
+        HIPCK(hipGetLastError());
+        return 0;
+    }));
+    HIPCK(hipMemcpyAsync(exposures, dH, NK * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(errors, derr, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(n_iterations, dnit, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(converged, dconv, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(n_exceed, dexceed, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(null_mean, dmean, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(null_errors, derr_b, NB * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(null_n_iterations, dnit_b, NB * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipStreamSynchronize(d.stream));
+    if (draws)  // plain counts: the clipped zeros restored to 0
+        for (size_t i = 0; i < (size_t)B * NV; ++i)
+            if (draws[i] < 1.0) draws[i] = 0.0;
     if (timings) {
         for (int i = 0; i < 3; ++i) {
             double total = 0.0;
