@@ -662,6 +662,40 @@ int salnmf_goodness_of_fit(int device, const double* counts, int64_t n_samples, 
                            int* n_exceed, double* null_mean, double* null_errors, int* null_n_iterations, double* draws,
                            double* timings);
 
+/* ---- Is signature s present in this sample?  A nested pair of fits against its own parametric-bootstrap null
+ * (csrc/salnmf_presence.h).  counts, signatures, the iteration arguments and chunk_bytes as
+ * salnmf_goodness_of_fit, plus max_iterations % conv_test_freq == 0 as salnmf_assign_signatures; test: n_test distinct signature
+ * indices in [0, n_signatures); candidates: NULL (every signature), or n_samples x n_signatures bytes as
+ * salnmf_assign_signatures_ex takes them (the set C_n, not empty).  Contract, for sample n and s = test[j]:
+ *   a SOLVE ON A SET A is salnmf_assign_signatures_ex's phase 0 with candidates = A: h_k = (sum_v x_v) / |A| on A and exactly 0.0
+ *   off it, the refit's step, objective and stop rule -- bit for bit the exposures, error, iteration count and convergence flag
+ *   of that call with candidates = required = A;
+ *   the alternative is the solve on C_n (h1, f1), the null the solve on C_n \ {s} (h0, f0); statistic[n, j] = f0 - f1, half the
+ *   likelihood-ratio statistic;
+ *   the pair is UNTESTED if s is not in C_n or C_n = {s}: tested[n, j] = 0, it draws nothing and costs no solve;
+ *   null draw b of the pair is one model draw (above, steps as salnmf_draw_model_counts) of sum_v counts[n, v] trials from the
+ *   exposures h0, with the Philox counter (q, 0x50530000 + s, n, b): the second word carries a stream family ("PS" in its upper
+ *   half) that no other draw uses -- the resampler's word is 0, the split's 0x53504C54, the goodness-of-fit draw's 0x474F4644 --
+ *   and the tested signature, so the draws of a pair depend on (seed, n, s, b) and on h0 only, not on n_samples, n_test,
+ *   n_draws, the chunks or what else is tested;
+ *   every draw goes through the same two solves from cold starts: null_statistics[b, n, j] = t_b;
+ *   reduction, one thread per pair in ascending b: n_exceed[n, j] counts t_b >= statistic[n, j] (false for a NaN on either
+ *   side), null_mean[n, j] is the sum of t_b from 0.0, divided by n_draws.  The p-value is (1 + n_exceed) / (n_draws + 1).
+ * Outputs: tested (1 / 0), statistic, n_exceed, null_mean, null_errors (f0)  n_samples x n_test;  null_exposures (h0)  n_samples x
+ * n_test x n_signatures;  exposures (h1)  n_samples x n_signatures and errors (f1)  n_samples -- every tested pair of a sample
+ * solves the same alternative; n_iterations, converged  n_samples x n_test x 2 (alternative, null);  null_statistics  n_draws x
+ * n_samples x n_test;  null_n_iterations  n_draws x n_samples x n_test x 2;  draws  NULL, or n_draws x n_samples x n_test x n_features,
+ * plain counts.  Entries of an untested pair: NaN in the doubles (0 in draws), 0 in the integers; a sample without a tested pair
+ * has NaN exposures and error.  timings: NULL, or 4 doubles -- milliseconds by device events of the draw launches, the solve
+ * launches and the reduction, and the number of chunks.
+ * Everything is validated on the host before any launch; status 1 and salnmf_last_error otherwise. */
+int salnmf_signature_presence(int device, const double* counts, int64_t n_samples, int n_features, const double* signatures,
+                              int n_signatures, const int* test, int n_test, const uint8_t* candidates, int n_draws, uint64_t seed,
+                              int min_iterations, int max_iterations, int conv_test_freq, double tol, int64_t chunk_bytes,
+                              uint8_t* tested, double* statistic, int* n_exceed, double* null_mean, double* exposures, double* errors,
+                              double* null_exposures, double* null_errors, int* n_iterations, int* converged,
+                              double* null_statistics, int* null_n_iterations, double* draws, double* timings);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,7 @@
 #include "salnmf_split.h"
 #define SALNMF_GOF_KERNELS 1
 #include "salnmf_gof.h"
+#include "salnmf_presence.h"
 #include "salnmf_stability.h"
 
 #include <algorithm>
@@ -316,6 +317,17 @@ void salnmf::gof_launch_model_draw(const double* H, const double* W, const uint3
 
 void salnmf::gof_launch_reduce(const GofReduceArgs& a, hipStream_t stream) {
     hipLaunchKernelGGL(gof_reduce_kernel, dim3((unsigned)((a.N + 255) / 256)), dim3(256), 0, stream, a);
+}
+
+// the presence test's draw (salnmf_presence.h): the same body, one workgroup per (pair, draw)
+void salnmf::presence_launch_draw(const double* H0, const double* W, const double* X, const int* pair_n, const int* pair_s, double* out, int64_t NP, int V,
+                                  int K, uint64_t seed, double floor, int first, int count, hipStream_t stream) {
+    for (int done = 0; done < count; done += GOF_GRID_Y) {
+        const int now = std::min(GOF_GRID_Y, count - done);
+        const PresenceDrawArgs a{H0, W, X, pair_n, pair_s, out + (size_t)done * NP * V, NP, V, K, (uint32_t)seed, (uint32_t)(seed >> 32), floor,
+                                 (uint32_t)(first + done)};
+        hipLaunchKernelGGL(presence_draw_kernel, dim3((unsigned)NP, (unsigned)now), dim3(RESAMPLE_BLOCK), 0, stream, a);
+    }
 }
 
 // ---- signature stability (salnmf_stability.h): the two feeders share everything after their own validation

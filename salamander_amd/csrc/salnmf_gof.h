@@ -9,7 +9,8 @@
 //   cum_v the 64-bit inclusive prefix sums of m, M = cum_{V-1} (M <= V 2^40 < 2^47);
 //   Philox4x32-10 (salnmf_resample.h: philox4x32_10), key = (seed & 0xffffffff, seed >> 32);
 //   block q of row n of draw b has counter (q, 0x474F4644, n, b) -- the resampler's second counter word is always 0 and the
-//   split's 0x53504C54, so the three streams never meet under one seed -- and gives the words (o0, o1, o2, o3);
+//   split's 0x53504C54, so the three streams never meet under one seed; the presence test's draws (salnmf_presence.h) use
+//   0x50530000 + s, a fourth family -- and gives the words (o0, o1, o2, o3);
 //   draw 2q uses u = o0 | o1 << 32, draw 2q + 1 uses u = o2 | o3 << 32, draws j >= T_n are discarded;
 //   t = floor(u M / 2^64) (the high 64 bits of the 128-bit product), and the draw lands in the smallest v with cum_v > t.
 // After the weights everything is integer arithmetic and the histogram is a sum of ones: the result does not depend on which
@@ -82,23 +83,23 @@ __device__ __forceinline__ double mul_then_add(double acc, double a, double b) {
     return acc + prod;
 }
 
-// One workgroup per (row, draw): blockIdx.x = row, blockIdx.y = draw - a.first.
-__global__ void __launch_bounds__(RESAMPLE_BLOCK) model_draw_kernel(ModelDrawArgs a) {
+// Row n of draw b by one workgroup, the body of every model draw: the exposures h (K), the stream word and the output row are
+// the caller's.  The trial count is *total, or with total == null sum_v (uint32) xrow[v].
+__device__ __forceinline__ void model_draw_row(const double* __restrict__ h, const double* __restrict__ W, const uint32_t* __restrict__ total,
+                                               const double* __restrict__ xrow, double* __restrict__ out, int V, int K, uint32_t key0, uint32_t key1,
+                                               uint32_t stream, uint32_t n, uint32_t b, double floor) {
     __shared__ double hs[GOF_KMAX];
     __shared__ double P[GOF_VMAX];
     __shared__ uint64_t cum[GOF_VMAX];
     __shared__ uint32_t hist[GOF_VMAX];
     __shared__ uint32_t trials;
     const int tid = threadIdx.x;
-    const int64_t n = blockIdx.x;
-    const uint32_t b = blockIdx.y + a.first;
-    const int V = a.V, K = a.K;
-    if (tid < K) hs[tid] = a.H[(size_t)n * K + tid];
+    if (tid < K) hs[tid] = h[tid];
     if (tid < V) hist[tid] = 0;
     __syncthreads();
     if (tid < V) {
         double p = 0.0;
-        for (int k = 0; k < K; ++k) p = mul_then_add(p, hs[k], a.W[k * V + tid]);
+        for (int k = 0; k < K; ++k) p = mul_then_add(p, hs[k], W[k * V + tid]);
         P[tid] = p;
     }
     __syncthreads();
@@ -106,10 +107,10 @@ __global__ void __launch_bounds__(RESAMPLE_BLOCK) model_draw_kernel(ModelDrawArg
         double S = 0.0;
         for (int v = 0; v < V; ++v) S += P[v];
         uint32_t T = 0;
-        if (a.totals)
-            T = a.totals[n];
+        if (total)
+            T = *total;
         else
-            for (int v = 0; v < V; ++v) T += (uint32_t)a.X[(size_t)n * V + v];
+            for (int v = 0; v < V; ++v) T += (uint32_t)xrow[v];
         if (!(S > 0.0) || !(S < __builtin_inf())) T = 0;
         if (T) {
             uint64_t c = 0;
@@ -125,14 +126,20 @@ __global__ void __launch_bounds__(RESAMPLE_BLOCK) model_draw_kernel(ModelDrawArg
         const uint32_t nblocks = (T >> 1) + (T & 1);
         for (uint32_t q = tid; q < nblocks; q += RESAMPLE_BLOCK) {
             uint32_t o[4];
-            philox4x32_10(q, GOF_STREAM, (uint32_t)n, b, a.key0, a.key1, o);
+            philox4x32_10(q, stream, n, b, key0, key1, o);
             atomicAdd(&hist[upper_cell64(__umul64hi((uint64_t)o[1] << 32 | o[0], M), cum, V)], 1u);
             if (2 * (uint64_t)q + 1 < T) atomicAdd(&hist[upper_cell64(__umul64hi((uint64_t)o[3] << 32 | o[2], M), cum, V)], 1u);
         }
     }
     __syncthreads();
-    double* out = a.out + ((size_t)blockIdx.y * a.N + n) * V;
-    if (tid < V) out[tid] = clipped_count(hist[tid], a.floor);
+    if (tid < V) out[tid] = clipped_count(hist[tid], floor);
+}
+
+// One workgroup per (row, draw): blockIdx.x = row, blockIdx.y = draw - a.first.
+__global__ void __launch_bounds__(RESAMPLE_BLOCK) model_draw_kernel(ModelDrawArgs a) {
+    const int64_t n = blockIdx.x;
+    model_draw_row(a.H + (size_t)n * a.K, a.W, a.totals ? a.totals + n : nullptr, a.X + (size_t)n * a.V, a.out + ((size_t)blockIdx.y * a.N + n) * a.V,
+                   a.V, a.K, a.key0, a.key1, GOF_STREAM, (uint32_t)n, blockIdx.y + a.first, a.floor);
 }
 
 // One thread per sample: the null divergences at or above the observed one, counted in ascending b (a NaN on either side

@@ -2,7 +2,8 @@
 // (salnmf_refit.h: refit_kernel, refit_reduce_kernel); and of the sparse assignment built on it
 // (salnmf_assign_signatures, salnmf_assign_signatures_ex; salnmf_assign.h: assign_kernel, assign_selection_kernel), DESIGN.md sections 14
 // and 14.1; and of the goodness-of-fit test built on it (salnmf_draw_model_counts, salnmf_goodness_of_fit; salnmf_gof.h:
-// model_draw_kernel, gof_reduce_kernel, which salnmf_batch.hip compiles), DESIGN.md section 16.
+// model_draw_kernel, gof_reduce_kernel, which salnmf_batch.hip compiles); and of the signature-presence test
+// (salnmf_signature_presence; salnmf_presence.h: presence_kernel here, presence_draw_kernel in salnmf_batch.hip), DESIGN.md section 17.
 #define SALNMF_TEMPLATES_ONLY 1
 #define SALNMF_REFIT_KERNELS 1
 #include "../../include/salnmf.h"
@@ -11,6 +12,7 @@
 #include "salnmf_refit.h"
 #include "salnmf_assign.h"
 #include "salnmf_gof.h"
+#include "salnmf_presence.h"
 
 #include <algorithm>
 #include <cmath>
@@ -144,6 +146,23 @@ int launch_assign(const AssignArgs& a, int cus, hipStream_t stream) {
         case 13: hipLaunchKernelGGL((assign_kernel<5, true>), grid, dim3(BLOCK), 0, stream, a); break;
         case 14: hipLaunchKernelGGL((assign_kernel<6, true>), grid, dim3(BLOCK), 0, stream, a); break;
         default: return fail("no assignment kernel for %d signatures", a.K);
+    }
+    HIPCK(hipGetLastError());
+    return 0;
+}
+
+int launch_presence(const PresenceArgs& a, int cus, hipStream_t stream) {
+    const int64_t ntiles = (a.P + 15) / 16;
+    const dim3 grid((unsigned)std::min<int64_t>((int64_t)cus, (ntiles + WAVES - 1) / WAVES));  // as launch_refit
+    HIPCK(hipMemsetAsync(a.next_tile, 0, sizeof(unsigned), stream));
+    switch ((a.K + 15) / 16) {
+        case 1: hipLaunchKernelGGL(presence_kernel<1>, grid, dim3(BLOCK), 0, stream, a); break;
+        case 2: hipLaunchKernelGGL(presence_kernel<2>, grid, dim3(BLOCK), 0, stream, a); break;
+        case 3: hipLaunchKernelGGL(presence_kernel<3>, grid, dim3(BLOCK), 0, stream, a); break;
+        case 4: hipLaunchKernelGGL(presence_kernel<4>, grid, dim3(BLOCK), 0, stream, a); break;
+        case 5: hipLaunchKernelGGL(presence_kernel<5>, grid, dim3(BLOCK), 0, stream, a); break;
+        case 6: hipLaunchKernelGGL(presence_kernel<6>, grid, dim3(BLOCK), 0, stream, a); break;
+        default: return fail("no presence kernel for %d signatures", a.K);
     }
     HIPCK(hipGetLastError());
     return 0;
@@ -592,6 +611,196 @@ extern "C" int salnmf_goodness_of_fit(int device, const double* counts, int64_t 
     if (draws)  // plain counts: the clipped zeros restored to 0
         for (size_t i = 0; i < (size_t)B * NV; ++i)
             if (draws[i] < 1.0) draws[i] = 0.0;
+    if (timings) {
+        for (int i = 0; i < 3; ++i) {
+            double total = 0.0;
+            for (const auto& pr : spans[i]) {
+                float ms = 0.f;
+                HIPCK(hipEventElapsedTime(&ms, pr.first, pr.second));
+                total += (double)ms;
+            }
+            timings[i] = total;
+        }
+        timings[3] = (double)n_chunks;
+    }
+    return 0;
+}
+
+// ---- is signature s present?  A nested pair of fits against its own bootstrap null (salnmf_presence.h)
+
+extern "C" int salnmf_signature_presence(int device, const double* counts, int64_t n_samples, int n_features, const double* signatures, int n_signatures,
+                                         const int* test, int n_test, const uint8_t* candidates, int n_draws, uint64_t seed, int min_iterations,
+                                         int max_iterations, int conv_test_freq, double tol, int64_t chunk_bytes, uint8_t* tested, double* statistic,
+                                         int* n_exceed, double* null_mean, double* exposures, double* errors, double* null_exposures, double* null_errors,
+                                         int* n_iterations, int* converged, double* null_statistics, int* null_n_iterations, double* draws,
+                                         double* timings) {
+    const int64_t N = n_samples;
+    const int V = n_features, K = n_signatures, S = n_test, B = n_draws;
+    if (!counts || !signatures || !test || !tested || !statistic || !n_exceed || !null_mean || !exposures || !errors || !null_exposures || !null_errors ||
+        !n_iterations || !converged || !null_statistics || !null_n_iterations)
+        return fail("null argument");
+    CK(gof_check_draws(B));
+    if (conv_test_freq >= 1 && max_iterations >= 0 && max_iterations % conv_test_freq != 0)
+        return fail("max_iterations must be a multiple of conv_test_freq, got %d and %d", max_iterations, conv_test_freq);
+    if (S < 1 || S > REFIT_KMAX) return fail("n_test must be in [1, %d], got %d", REFIT_KMAX, S);
+    for (int j = 0; j < S; ++j) {
+        if (test[j] < 0 || test[j] >= K) return fail("tested signature %d is not in [0, %d)", test[j], K);
+        for (int i = 0; i < j; ++i)
+            if (test[i] == test[j]) return fail("signature %d is tested twice", test[j]);
+    }
+    RefitInputs in;
+    CK(refit_prepare(device, counts, N, V, signatures, K, 0, 0, nullptr, min_iterations, max_iterations, conv_test_freq, tol, true, in,
+                     AssignSets{candidates, nullptr, 0}));
+    CK(refit_check_counts(counts, N, V, in.icounts));  // integer counts, row totals below 2^32 (the values themselves are not used)
+    const int cus = in.cus;
+    const int words = ((K + 15) / 16 + 1) / 2;
+
+    // the tested pairs, sample after sample: s is a candidate and not the only one
+    const size_t NS = (size_t)N * S, NV = (size_t)N * V, NK = (size_t)N * K;
+    std::vector<int> pair_n, pair_s;
+    std::vector<size_t> slot;  // pair j is entry slot[j] of the (N, S) results
+    for (int64_t n = 0; n < N; ++n) {
+        int size = K;
+        if (candidates) {
+            size = 0;
+            for (int w = 0; w < words; ++w) size += __builtin_popcount(in.cand[(size_t)n * words + w]);
+        }
+        for (int j = 0; j < S; ++j) {
+            const int s = test[j];
+            const bool member = !candidates || ((in.cand[(size_t)n * words + (s >> 5)] >> (s & 31)) & 1u);
+            tested[(size_t)n * S + j] = member && size > 1;
+            if (member && size > 1) pair_n.push_back((int)n), pair_s.push_back(s), slot.push_back((size_t)n * S + j);
+        }
+    }
+    const size_t NP = pair_n.size();
+    if (NP > 0x7fffffff) return fail("%zu tested pairs: at most 2^31 - 1", NP);
+    const double nan = std::nan("");
+    std::fill(statistic, statistic + NS, nan);
+    std::fill(null_mean, null_mean + NS, nan);
+    std::fill(null_errors, null_errors + NS, nan);
+    std::fill(n_exceed, n_exceed + NS, 0);
+    std::fill(exposures, exposures + NK, nan);
+    std::fill(errors, errors + N, nan);
+    std::fill(null_exposures, null_exposures + NS * K, nan);
+    std::fill(n_iterations, n_iterations + 2 * NS, 0);
+    std::fill(converged, converged + 2 * NS, 0);
+    std::fill(null_statistics, null_statistics + (size_t)B * NS, nan);
+    std::fill(null_n_iterations, null_n_iterations + 2 * (size_t)B * NS, 0);
+    if (draws) std::fill(draws, draws + (size_t)B * NS * V, 0.0);
+    if (timings) timings[0] = timings[1] = timings[2] = timings[3] = 0.0;
+    if (NP == 0) return 0;
+
+    // draws per chunk: the [chunk][pairs][V] buffer stays within chunk_bytes (at least one draw)
+    const size_t PV = NP * V, PK = NP * K, PB = NP * B;
+    const int64_t budget = chunk_bytes > 0 ? chunk_bytes : (int64_t)256 << 20;
+    const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(B, budget / (int64_t)(sizeof(double) * PV)));
+
+    // (host buffers of the asynchronous copies live until d's destructor has waited for the stream)
+    std::vector<double> h_stat(NP), h_f(2 * NP), h_H1(PK), h_H0(PK), h_mean(NP), h_stat_b(PB), h_draws(draws ? PB * V : 0);
+    std::vector<int> h_nit(2 * NP), h_conv(2 * NP), h_exceed(NP), h_nit_b(2 * PB);
+    DevBufs d;
+    CK(d.own_stream());
+    double* dW = d.get<double>((size_t)K * V);
+    double* dX = d.get<double>(NV);
+    int* dpn = d.get<int>(NP);
+    int* dps = d.get<int>(NP);
+    double* dstat = d.get<double>(NP);
+    double* df = d.get<double>(2 * NP);
+    int* dnit = d.get<int>(2 * NP);
+    int* dconv = d.get<int>(2 * NP);
+    double* dH1 = d.get<double>(PK);
+    double* dH0 = d.get<double>(PK);
+    unsigned* dnext = d.get<unsigned>(1);
+    double* dXb = d.get<double>((size_t)chunk * PV);
+    double* dstat_b = d.get<double>(PB);
+    int* dnit_b = d.get<int>(2 * PB);
+    int* dexceed = d.get<int>(NP);
+    double* dmean = d.get<double>(NP);
+    uint32_t* dcand = candidates ? d.get<uint32_t>(in.cand.size()) : nullptr;
+    if (!dW || !dX || !dpn || !dps || !dstat || !df || !dnit || !dconv || !dH1 || !dH0 || !dnext || !dXb || !dstat_b || !dnit_b || !dexceed || !dmean ||
+        (candidates && !dcand))
+        return fail("hipMalloc failed (%d draws of %zu pairs x %d, %d signatures)", B, NP, V, K);
+    HIPCK(hipMemcpyAsync(dW, signatures, (size_t)K * V * sizeof(double), hipMemcpyHostToDevice, d.stream));
+    HIPCK(hipMemcpyAsync(dX, in.x.data(), NV * sizeof(double), hipMemcpyHostToDevice, d.stream));
+    HIPCK(hipMemcpyAsync(dpn, pair_n.data(), NP * sizeof(int), hipMemcpyHostToDevice, d.stream));
+    HIPCK(hipMemcpyAsync(dps, pair_s.data(), NP * sizeof(int), hipMemcpyHostToDevice, d.stream));
+    if (dcand) HIPCK(hipMemcpyAsync(dcand, in.cand.data(), in.cand.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> spans[3];  // draw, solve, reduce
+    auto timed = [&](int which, auto&& body) -> int {
+        hipEvent_t e0 = timings ? d.mark() : nullptr;
+        CK(body());
+        hipEvent_t e1 = timings ? d.mark() : nullptr;
+        if (timings && (!e0 || !e1)) return fail("event record failed");
+        if (timings) spans[which].emplace_back(e0, e1);
+        return 0;
+    };
+    const PresenceArgs a{dX, dW, dpn, dps, dcand, dstat, dnit, df, dconv, dH1, dH0, dnext, (int64_t)NP, (int64_t)NP, V, K, 1,
+                         min_iterations, max_iterations, conv_test_freq, tol};
+    CK(timed(1, [&] { return launch_presence(a, cus, d.stream); }));
+    int n_chunks = 0;
+    for (int first = 0; first < B; first += chunk, ++n_chunks) {
+        const int count = std::min(chunk, B - first);
+        // from the device-resident exposures of the observed null fits; a row's trial count is read off the clipped counts
+        CK(timed(0, [&]() -> int {
+            presence_launch_draw(dH0, dW, dX, dpn, dps, dXb, (int64_t)NP, V, K, seed, SALNMF_EPSILON, first, count, d.stream);
+            HIPCK(hipGetLastError());
+            return 0;
+        }));
+        if (draws) HIPCK(hipMemcpyAsync(h_draws.data() + (size_t)first * PV, dXb, (size_t)count * PV * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+        // a draw's problems keep their statistic and iteration counts only
+        PresenceArgs c = a;
+        c.X = dXb;
+        c.by_sample = 0;
+        c.P = (int64_t)count * (int64_t)NP;
+        c.stat = dstat_b + (size_t)first * NP;
+        c.nit = dnit_b + 2 * (size_t)first * NP;
+        c.f = nullptr, c.conv = nullptr, c.H1 = nullptr, c.H0 = nullptr;
+        CK(timed(1, [&] { return launch_presence(c, cus, d.stream); }));
+    }
+    // gof_reduce_kernel over the pairs: n_exceed counts t_b >= t (false for a NaN on either side), null_mean sums from 0.0 in ascending b
+    const GofReduceArgs red{dstat, dstat_b, dexceed, dmean, (int64_t)NP, B};
+    CK(timed(2, [&]() -> int {
+        gof_launch_reduce(red, d.stream);
+        HIPCK(hipGetLastError());
+        return 0;
+    }));
+    HIPCK(hipMemcpyAsync(h_stat.data(), dstat, NP * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(h_f.data(), df, 2 * NP * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(h_nit.data(), dnit, 2 * NP * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(h_conv.data(), dconv, 2 * NP * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(h_H1.data(), dH1, PK * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(h_H0.data(), dH0, PK * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(h_exceed.data(), dexceed, NP * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(h_mean.data(), dmean, NP * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(h_stat_b.data(), dstat_b, PB * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(h_nit_b.data(), dnit_b, 2 * PB * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipStreamSynchronize(d.stream));
+
+    // the compact pair list back into the (N, S) results; a sample's alternative fit is that of its first tested pair (every
+    // tested pair of a sample solves the same problem on C and holds the same bits)
+    for (size_t j = 0; j < NP; ++j) {
+        const size_t o = slot[j], n = (size_t)pair_n[j];
+        statistic[o] = h_stat[j];
+        n_exceed[o] = h_exceed[j];
+        null_mean[o] = h_mean[j];
+        null_errors[o] = h_f[2 * j + 1];
+        std::copy(h_H0.begin() + j * K, h_H0.begin() + (j + 1) * K, null_exposures + o * K);
+        for (int i = 0; i < 2; ++i) n_iterations[2 * o + i] = h_nit[2 * j + i], converged[2 * o + i] = h_conv[2 * j + i];
+        if (j == 0 || (size_t)pair_n[j - 1] != n) {
+            std::copy(h_H1.begin() + j * K, h_H1.begin() + (j + 1) * K, exposures + n * K);
+            errors[n] = h_f[2 * j];
+        }
+        for (size_t b = 0; b < (size_t)B; ++b) {
+            null_statistics[b * NS + o] = h_stat_b[b * NP + j];
+            for (int i = 0; i < 2; ++i) null_n_iterations[2 * (b * NS + o) + i] = h_nit_b[2 * (b * NP + j) + i];
+            if (draws)  // plain counts: the clipped zeros restored to 0
+                for (int v = 0; v < V; ++v) {
+                    const double c = h_draws[(b * NP + j) * V + v];
+                    draws[(b * NS + o) * V + v] = c < 1.0 ? 0.0 : c;
+                }
+        }
+    }
     if (timings) {
         for (int i = 0; i < 3; ++i) {
             double total = 0.0;
