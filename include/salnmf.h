@@ -696,6 +696,49 @@ int salnmf_signature_presence(int device, const double* counts, int64_t n_sample
                               double* null_exposures, double* null_errors, int* n_iterations, int* converged,
                               double* null_statistics, int* null_n_iterations, double* draws, double* timings);
 
+/* ---- Could the presence test have seen signature s in this sample?  Detection power per (sample, tested signature, share)
+ * (csrc/salnmf_power.h).  The arguments of salnmf_signature_presence, then shares: n_shares doubles in
+ * [0, 1), strictly ascending; n_alt_draws (A) draws per share; max_exceed: a draw is detected with at most this many null
+ * statistics at or above its own -- for a level alpha the largest m >= 0 with (1 + m) / (n_draws + 1) <= alpha, so that
+ * "detected" is "the presence test would have given p <= alpha against this null".  Contract, for sample n, s = test[j], share
+ * pi_l = shares[l] and alternative draw a:
+ *   the presence test runs first, unchanged: its launches, and its outputs bit for bit those of salnmf_signature_presence with
+ *   the same arguments; untested pairs stay untested here (NaN in the doubles below, 0 in the integers and the draws, no cost);
+ *   planted_exposures[l, n, j, :]: with h0 the pair's null fit where the observed launch left it on the device, S0 = sum_k h0[k]
+ *   from 0.0 in ascending k over all n_signatures, c_l = 1.0 - pi_l (one rounded subtraction): Hp[k] = c_l h0[k] for k != s and
+ *   Hp[s] = pi_l S0, each one rounded product, no fused multiply-add.  h0[s] is exactly 0, so pi = 0 gives h0 back bit for bit;
+ *   alternative draw a of (pair, l) is one model draw (salnmf_draw_model_counts' steps) of sum_v counts[n, v] trials from that
+ *   planted row, with the Philox counter (q, 0x50570000 + s, n, a): a stream family of its own ("PW" in the upper half of the
+ *   second word).  The level is not in the counter -- all levels of a pair share their random numbers -- so the draw depends on
+ *   (seed, n, s, a) and on its planted row and on nothing else: not n_samples, n_test, n_shares, n_alt_draws, n_draws, the
+ *   chunks or the other shares;
+ *   every draw goes through the presence test's two solves from cold starts: alt_statistics[l, a, n, j] = t*_a and
+ *   alt_n_iterations[l, a, n, j, 2], in chunks of rows r = l A + a whose buffer stays within chunk_bytes;
+ *   reduction, one thread per (pair, share), everything in ascending order: alt_n_exceed[l, a, n, j] counts the pair's n_draws
+ *   null statistics t_b >= t*_a (false for a NaN on either side); draw a is detected iff t*_a is not NaN and that count is
+ *   <= max_exceed; n_detected[l, n, j] counts the detected draws; alt_mean[l, n, j] is the sum of t*_a from 0.0 in ascending a,
+ *   divided by A.  Power is n_detected / A.
+ * The critical value is that of the null drawn from the OBSERVED sample's h0, not re-estimated per alternative draw (that
+ * would be a nested bootstrap of A n_draws draws): power at pi = 0 measures this approximation and should sit near alpha.  The
+ * planted signature displaces the fitted background proportionally; everything is conditional on the sample's total.
+ * Outputs: those of salnmf_signature_presence, then planted_exposures  n_shares x n_samples x n_test x n_signatures;
+ * alt_statistics, alt_n_exceed  n_shares x A x n_samples x n_test;  alt_n_iterations  the same x 2;  n_detected, alt_mean
+ * n_shares x n_samples x n_test;  alt_draws  NULL, or n_shares x A x n_samples x n_test x n_features, plain counts.  timings: NULL,
+ * or 9 doubles -- the presence test's four, then milliseconds by device events of the planting, the alternative draw launches,
+ * the alternative solve launches and the power reduction, and the number of chunks of alternative draws.
+ * Refused on the host before any launch, status 1 and salnmf_last_error: everything salnmf_signature_presence refuses; n_shares
+ * outside [1, 64]; a share that is not finite, is < 0 or >= 1, or is not strictly above its predecessor; n_alt_draws outside
+ * [1, 65536]; max_exceed outside [0, n_draws]. */
+int salnmf_signature_power(int device, const double* counts, int64_t n_samples, int n_features, const double* signatures,
+                           int n_signatures, const int* test, int n_test, const uint8_t* candidates, int n_draws, uint64_t seed,
+                           int min_iterations, int max_iterations, int conv_test_freq, double tol, int64_t chunk_bytes,
+                           const double* shares, int n_shares, int n_alt_draws, int max_exceed,
+                           uint8_t* tested, double* statistic, int* n_exceed, double* null_mean, double* exposures, double* errors,
+                           double* null_exposures, double* null_errors, int* n_iterations, int* converged,
+                           double* null_statistics, int* null_n_iterations, double* draws,
+                           double* planted_exposures, double* alt_statistics, int* alt_n_iterations, int* alt_n_exceed,
+                           int* n_detected, double* alt_mean, double* alt_draws, double* timings);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@ from .anndata_compat import AnnData, MuData
 from .assign import AssignResult, assign_signatures
 from .engine import Engine
 from .gof import GofResult, draw_model_counts, goodness_of_fit
+from .power import PowerResult, signature_power
 from .presence import PresenceResult, signature_presence_test
 from .refit import RefitResult, refit_exposures
 from .resample import resample_counts
@@ -21,4 +22,4 @@ from .stability import signature_stability
 __version__ = "0.1.0"
 __all__ = ["models", "Engine", "AnnData", "MuData", "EngineUnavailable", "resample_counts", "signature_stability", "refit_exposures", "RefitResult", "assign_signatures",
            "AssignResult", "split_counts", "goodness_of_fit", "draw_model_counts", "GofResult", "signature_presence_test",
-           "PresenceResult"]
+           "PresenceResult", "signature_power", "PowerResult"]

@@ -146,6 +146,10 @@ SIGNATURES = {
     # presence of single signatures by a nested pair of fits: salamander_amd/presence.py
     "salnmf_signature_presence": (c_int, [c_int, _D, c_int64, c_int, _D, c_int, _I, c_int, POINTER(c_uint8), c_int, c_uint64, c_int, c_int, c_int,
                                           c_double, c_int64, POINTER(c_uint8), _D, _I, _D, _D, _D, _D, _D, _I, _I, _D, _I, _D, _D]),
+    # the presence test's detection power and limit: salamander_amd/power.py
+    "salnmf_signature_power": (c_int, [c_int, _D, c_int64, c_int, _D, c_int, _I, c_int, POINTER(c_uint8), c_int, c_uint64, c_int, c_int, c_int,
+                                       c_double, c_int64, _D, c_int, c_int, c_int, POINTER(c_uint8), _D, _I, _D, _D, _D, _D, _D, _I, _I, _D, _I, _D,
+                                       _D, _D, _I, _I, _I, _D, _D, _D]),
 }
 
 OBJECTIVE_SLOTS = 256  # SALNMF_OBJECTIVE_SLOTS

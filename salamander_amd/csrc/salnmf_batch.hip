@@ -14,6 +14,7 @@
 #define SALNMF_GOF_KERNELS 1
 #include "salnmf_gof.h"
 #include "salnmf_presence.h"
+#include "salnmf_power.h"
 #include "salnmf_stability.h"
 
 #include <algorithm>
@@ -328,6 +329,25 @@ void salnmf::presence_launch_draw(const double* H0, const double* W, const doubl
                                  (uint32_t)(first + done)};
         hipLaunchKernelGGL(presence_draw_kernel, dim3((unsigned)NP, (unsigned)now), dim3(RESAMPLE_BLOCK), 0, stream, a);
     }
+}
+
+// the power analysis of the presence test (salnmf_power.h): planting, the draw with the same body, the reduction
+void salnmf::power_launch_plant(const PowerPlantArgs& a, hipStream_t stream) {
+    hipLaunchKernelGGL(power_plant_kernel, dim3((unsigned)((a.NP * a.L + 255) / 256)), dim3(256), 0, stream, a);
+}
+
+void salnmf::power_launch_draw(const double* Hp, const double* W, const double* X, const int* pair_n, const int* pair_s, double* out, int64_t NP, int V,
+                               int K, uint64_t seed, double floor, int n_alt_draws, int64_t first, int64_t count, hipStream_t stream) {
+    for (int64_t done = 0; done < count; done += GOF_GRID_Y) {
+        const int now = (int)std::min<int64_t>(GOF_GRID_Y, count - done);
+        const PowerDrawArgs a{Hp, W, X, pair_n, pair_s, out + (size_t)done * NP * V, NP, V, K, (uint32_t)seed, (uint32_t)(seed >> 32), floor,
+                              (uint32_t)(first + done), (uint32_t)n_alt_draws};
+        hipLaunchKernelGGL(power_draw_kernel, dim3((unsigned)NP, (unsigned)now), dim3(RESAMPLE_BLOCK), 0, stream, a);
+    }
+}
+
+void salnmf::power_launch_reduce(const PowerReduceArgs& a, hipStream_t stream) {
+    hipLaunchKernelGGL(power_reduce_kernel, dim3((unsigned)((a.NP * a.L + 255) / 256)), dim3(256), 0, stream, a);
 }
 
 // ---- signature stability (salnmf_stability.h): the two feeders share everything after their own validation

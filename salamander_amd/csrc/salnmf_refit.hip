@@ -3,7 +3,8 @@
 // (salnmf_assign_signatures, salnmf_assign_signatures_ex; salnmf_assign.h: assign_kernel, assign_selection_kernel), DESIGN.md sections 14
 // and 14.1; and of the goodness-of-fit test built on it (salnmf_draw_model_counts, salnmf_goodness_of_fit; salnmf_gof.h:
 // model_draw_kernel, gof_reduce_kernel, which salnmf_batch.hip compiles); and of the signature-presence test
-// (salnmf_signature_presence; salnmf_presence.h: presence_kernel here, presence_draw_kernel in salnmf_batch.hip), DESIGN.md section 17.
+// (salnmf_signature_presence; salnmf_presence.h: presence_kernel here, presence_draw_kernel in salnmf_batch.hip), DESIGN.md section 17;
+// and of that test's power analysis (salnmf_signature_power; salnmf_power.h: its three kernels in salnmf_batch.hip), DESIGN.md section 18.
 #define SALNMF_TEMPLATES_ONLY 1
 #define SALNMF_REFIT_KERNELS 1
 #include "../../include/salnmf.h"
@@ -13,9 +14,11 @@
 #include "salnmf_assign.h"
 #include "salnmf_gof.h"
 #include "salnmf_presence.h"
+#include "salnmf_power.h"
 
 #include <algorithm>
 #include <cmath>
+#include <memory>
 #include <vector>
 
 using namespace salnmf;
@@ -626,30 +629,102 @@ extern "C" int salnmf_goodness_of_fit(int device, const double* counts, int64_t 
     return 0;
 }
 
-// ---- is signature s present?  A nested pair of fits against its own bootstrap null (salnmf_presence.h)
+// ---- is signature s present?  A nested pair of fits against its own bootstrap null (salnmf_presence.h);
+// and could the test have seen it?  (salnmf_power.h).  Both entry points run presence_enqueue and
+// presence_finish; the power analysis puts its launches on the same stream in between.
 
-extern "C" int salnmf_signature_presence(int device, const double* counts, int64_t n_samples, int n_features, const double* signatures, int n_signatures,
-                                         const int* test, int n_test, const uint8_t* candidates, int n_draws, uint64_t seed, int min_iterations,
-                                         int max_iterations, int conv_test_freq, double tol, int64_t chunk_bytes, uint8_t* tested, double* statistic,
-                                         int* n_exceed, double* null_mean, double* exposures, double* errors, double* null_exposures, double* null_errors,
-                                         int* n_iterations, int* converged, double* null_statistics, int* null_n_iterations, double* draws,
-                                         double* timings) {
-    const int64_t N = n_samples;
-    const int V = n_features, K = n_signatures, S = n_test, B = n_draws;
-    if (!counts || !signatures || !test || !tested || !statistic || !n_exceed || !null_mean || !exposures || !errors || !null_exposures || !null_errors ||
-        !n_iterations || !converged || !null_statistics || !null_n_iterations)
+namespace {
+
+// salnmf_signature_presence's arguments
+struct PresenceIO {
+    int device;
+    const double* counts;
+    int64_t N;
+    int V;
+    const double* signatures;
+    int K;
+    const int* test;
+    int S;
+    const uint8_t* candidates;
+    int B;
+    uint64_t seed;
+    int min_iterations, max_iterations, conv_test_freq;
+    double tol;
+    int64_t chunk_bytes;
+    uint8_t* tested;
+    double* statistic;
+    int* n_exceed;
+    double *null_mean, *exposures, *errors, *null_exposures, *null_errors;
+    int *n_iterations, *converged;
+    double* null_statistics;
+    int* null_n_iterations;
+    double *draws, *timings;
+};
+
+// What a call keeps between its launches and its results: the pair list, the device buffers and the host ends of the
+// asynchronous copies (which live until d's destructor has waited for the stream: d is the last member, and exists once the
+// validation has passed and a pair is tested).
+struct PresenceRun {
+    RefitInputs in;
+    std::vector<int> pair_n, pair_s;
+    std::vector<size_t> slot;  // pair j is entry slot[j] of the (N, S) results
+    std::vector<double> h_stat, h_f, h_H1, h_H0, h_mean, h_stat_b, h_draws;
+    std::vector<int> h_nit, h_conv, h_exceed, h_nit_b;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> spans[7];  // draw, solve, reduce; planting, alternative draw, solve, reduce
+    size_t NP = 0;
+    int64_t chunk_rows = 0;  // rows [pairs][V] of the chunk buffer that chunk_bytes allows
+    int n_chunks = 0;
+    bool timing = false;
+    double *dW = nullptr, *dX = nullptr, *dH0 = nullptr, *dstat_b = nullptr, *dXb = nullptr;
+    int *dpn = nullptr, *dps = nullptr;
+    PresenceArgs a{};  // the observed launch's
+    std::unique_ptr<DevBufs> d;
+
+    template <typename F>
+    int timed(int which, F&& body) {
+        hipEvent_t e0 = timing ? d->mark() : nullptr;
+        CK(body());
+        hipEvent_t e1 = timing ? d->mark() : nullptr;
+        if (timing && (!e0 || !e1)) return fail("event record failed");
+        if (timing) spans[which].emplace_back(e0, e1);
+        return 0;
+    }
+    int span_ms(int which, double* out) {
+        double total = 0.0;
+        for (const auto& pr : spans[which]) {
+            float ms = 0.f;
+            HIPCK(hipEventElapsedTime(&ms, pr.first, pr.second));
+            total += (double)ms;
+        }
+        *out = total;
+        return 0;
+    }
+};
+
+// Validation, the pair list, the untested entries of the results, and -- with a tested pair -- everything the presence test puts
+// on the stream: the uploads, the observed launch, the null chunks, the reduction and the downloads.  Nothing is waited for.  h0
+// (r.dH0, [pairs][K]) and the null statistics (r.dstat_b, [B][pairs]) stay on the device; the chunk buffer r.dXb holds
+// min(max(B, other_rows), r.chunk_rows) rows, so that a caller with other_rows draws of its own can reuse it.
+int presence_enqueue(const PresenceIO& io, int64_t other_rows, PresenceRun& r) {
+    const int64_t N = io.N;
+    const int V = io.V, K = io.K, S = io.S, B = io.B;
+    const double* counts = io.counts;
+    const int* test = io.test;
+    const uint8_t* candidates = io.candidates;
+    if (!counts || !io.signatures || !test || !io.tested || !io.statistic || !io.n_exceed || !io.null_mean || !io.exposures || !io.errors ||
+        !io.null_exposures || !io.null_errors || !io.n_iterations || !io.converged || !io.null_statistics || !io.null_n_iterations)
         return fail("null argument");
     CK(gof_check_draws(B));
-    if (conv_test_freq >= 1 && max_iterations >= 0 && max_iterations % conv_test_freq != 0)
-        return fail("max_iterations must be a multiple of conv_test_freq, got %d and %d", max_iterations, conv_test_freq);
+    if (io.conv_test_freq >= 1 && io.max_iterations >= 0 && io.max_iterations % io.conv_test_freq != 0)
+        return fail("max_iterations must be a multiple of conv_test_freq, got %d and %d", io.max_iterations, io.conv_test_freq);
     if (S < 1 || S > REFIT_KMAX) return fail("n_test must be in [1, %d], got %d", REFIT_KMAX, S);
     for (int j = 0; j < S; ++j) {
         if (test[j] < 0 || test[j] >= K) return fail("tested signature %d is not in [0, %d)", test[j], K);
         for (int i = 0; i < j; ++i)
             if (test[i] == test[j]) return fail("signature %d is tested twice", test[j]);
     }
-    RefitInputs in;
-    CK(refit_prepare(device, counts, N, V, signatures, K, 0, 0, nullptr, min_iterations, max_iterations, conv_test_freq, tol, true, in,
+    RefitInputs& in = r.in;
+    CK(refit_prepare(io.device, counts, N, V, io.signatures, K, 0, 0, nullptr, io.min_iterations, io.max_iterations, io.conv_test_freq, io.tol, true, in,
                      AssignSets{candidates, nullptr, 0}));
     CK(refit_check_counts(counts, N, V, in.icounts));  // integer counts, row totals below 2^32 (the values themselves are not used)
     const int cus = in.cus;
@@ -657,8 +732,7 @@ extern "C" int salnmf_signature_presence(int device, const double* counts, int64
 
     // the tested pairs, sample after sample: s is a candidate and not the only one
     const size_t NS = (size_t)N * S, NV = (size_t)N * V, NK = (size_t)N * K;
-    std::vector<int> pair_n, pair_s;
-    std::vector<size_t> slot;  // pair j is entry slot[j] of the (N, S) results
+    std::vector<int>&pair_n = r.pair_n, &pair_s = r.pair_s;
     for (int64_t n = 0; n < N; ++n) {
         int size = K;
         if (candidates) {
@@ -668,51 +742,55 @@ extern "C" int salnmf_signature_presence(int device, const double* counts, int64
         for (int j = 0; j < S; ++j) {
             const int s = test[j];
             const bool member = !candidates || ((in.cand[(size_t)n * words + (s >> 5)] >> (s & 31)) & 1u);
-            tested[(size_t)n * S + j] = member && size > 1;
-            if (member && size > 1) pair_n.push_back((int)n), pair_s.push_back(s), slot.push_back((size_t)n * S + j);
+            io.tested[(size_t)n * S + j] = member && size > 1;
+            if (member && size > 1) pair_n.push_back((int)n), pair_s.push_back(s), r.slot.push_back((size_t)n * S + j);
         }
     }
     const size_t NP = pair_n.size();
     if (NP > 0x7fffffff) return fail("%zu tested pairs: at most 2^31 - 1", NP);
     const double nan = std::nan("");
-    std::fill(statistic, statistic + NS, nan);
-    std::fill(null_mean, null_mean + NS, nan);
-    std::fill(null_errors, null_errors + NS, nan);
-    std::fill(n_exceed, n_exceed + NS, 0);
-    std::fill(exposures, exposures + NK, nan);
-    std::fill(errors, errors + N, nan);
-    std::fill(null_exposures, null_exposures + NS * K, nan);
-    std::fill(n_iterations, n_iterations + 2 * NS, 0);
-    std::fill(converged, converged + 2 * NS, 0);
-    std::fill(null_statistics, null_statistics + (size_t)B * NS, nan);
-    std::fill(null_n_iterations, null_n_iterations + 2 * (size_t)B * NS, 0);
-    if (draws) std::fill(draws, draws + (size_t)B * NS * V, 0.0);
-    if (timings) timings[0] = timings[1] = timings[2] = timings[3] = 0.0;
+    std::fill(io.statistic, io.statistic + NS, nan);
+    std::fill(io.null_mean, io.null_mean + NS, nan);
+    std::fill(io.null_errors, io.null_errors + NS, nan);
+    std::fill(io.n_exceed, io.n_exceed + NS, 0);
+    std::fill(io.exposures, io.exposures + NK, nan);
+    std::fill(io.errors, io.errors + N, nan);
+    std::fill(io.null_exposures, io.null_exposures + NS * K, nan);
+    std::fill(io.n_iterations, io.n_iterations + 2 * NS, 0);
+    std::fill(io.converged, io.converged + 2 * NS, 0);
+    std::fill(io.null_statistics, io.null_statistics + (size_t)B * NS, nan);
+    std::fill(io.null_n_iterations, io.null_n_iterations + 2 * (size_t)B * NS, 0);
+    if (io.draws) std::fill(io.draws, io.draws + (size_t)B * NS * V, 0.0);
+    if (io.timings) io.timings[0] = io.timings[1] = io.timings[2] = io.timings[3] = 0.0;
+    r.NP = NP;
     if (NP == 0) return 0;
 
     // draws per chunk: the [chunk][pairs][V] buffer stays within chunk_bytes (at least one draw)
     const size_t PV = NP * V, PK = NP * K, PB = NP * B;
-    const int64_t budget = chunk_bytes > 0 ? chunk_bytes : (int64_t)256 << 20;
-    const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(B, budget / (int64_t)(sizeof(double) * PV)));
+    const int64_t budget = io.chunk_bytes > 0 ? io.chunk_bytes : (int64_t)256 << 20;
+    r.chunk_rows = std::max<int64_t>(1, budget / (int64_t)(sizeof(double) * PV));
+    const int chunk = (int)std::min<int64_t>(B, r.chunk_rows);
+    const int64_t buffer_rows = std::min<int64_t>(std::max<int64_t>(B, other_rows), r.chunk_rows);
 
-    // (host buffers of the asynchronous copies live until d's destructor has waited for the stream)
-    std::vector<double> h_stat(NP), h_f(2 * NP), h_H1(PK), h_H0(PK), h_mean(NP), h_stat_b(PB), h_draws(draws ? PB * V : 0);
-    std::vector<int> h_nit(2 * NP), h_conv(2 * NP), h_exceed(NP), h_nit_b(2 * PB);
-    DevBufs d;
+    r.h_stat.resize(NP), r.h_f.resize(2 * NP), r.h_H1.resize(PK), r.h_H0.resize(PK), r.h_mean.resize(NP), r.h_stat_b.resize(PB);
+    r.h_draws.resize(io.draws ? PB * V : 0);
+    r.h_nit.resize(2 * NP), r.h_conv.resize(2 * NP), r.h_exceed.resize(NP), r.h_nit_b.resize(2 * PB);
+    r.d.reset(new DevBufs);
+    DevBufs& d = *r.d;
     CK(d.own_stream());
-    double* dW = d.get<double>((size_t)K * V);
-    double* dX = d.get<double>(NV);
-    int* dpn = d.get<int>(NP);
-    int* dps = d.get<int>(NP);
+    double* dW = r.dW = d.get<double>((size_t)K * V);
+    double* dX = r.dX = d.get<double>(NV);
+    int* dpn = r.dpn = d.get<int>(NP);
+    int* dps = r.dps = d.get<int>(NP);
     double* dstat = d.get<double>(NP);
     double* df = d.get<double>(2 * NP);
     int* dnit = d.get<int>(2 * NP);
     int* dconv = d.get<int>(2 * NP);
     double* dH1 = d.get<double>(PK);
-    double* dH0 = d.get<double>(PK);
+    double* dH0 = r.dH0 = d.get<double>(PK);
     unsigned* dnext = d.get<unsigned>(1);
-    double* dXb = d.get<double>((size_t)chunk * PV);
-    double* dstat_b = d.get<double>(PB);
+    double* dXb = r.dXb = d.get<double>((size_t)buffer_rows * PV);
+    double* dstat_b = r.dstat_b = d.get<double>(PB);
     int* dnit_b = d.get<int>(2 * PB);
     int* dexceed = d.get<int>(NP);
     double* dmean = d.get<double>(NP);
@@ -720,34 +798,26 @@ extern "C" int salnmf_signature_presence(int device, const double* counts, int64
     if (!dW || !dX || !dpn || !dps || !dstat || !df || !dnit || !dconv || !dH1 || !dH0 || !dnext || !dXb || !dstat_b || !dnit_b || !dexceed || !dmean ||
         (candidates && !dcand))
         return fail("hipMalloc failed (%d draws of %zu pairs x %d, %d signatures)", B, NP, V, K);
-    HIPCK(hipMemcpyAsync(dW, signatures, (size_t)K * V * sizeof(double), hipMemcpyHostToDevice, d.stream));
+    HIPCK(hipMemcpyAsync(dW, io.signatures, (size_t)K * V * sizeof(double), hipMemcpyHostToDevice, d.stream));
     HIPCK(hipMemcpyAsync(dX, in.x.data(), NV * sizeof(double), hipMemcpyHostToDevice, d.stream));
     HIPCK(hipMemcpyAsync(dpn, pair_n.data(), NP * sizeof(int), hipMemcpyHostToDevice, d.stream));
     HIPCK(hipMemcpyAsync(dps, pair_s.data(), NP * sizeof(int), hipMemcpyHostToDevice, d.stream));
     if (dcand) HIPCK(hipMemcpyAsync(dcand, in.cand.data(), in.cand.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
 
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> spans[3];  // draw, solve, reduce
-    auto timed = [&](int which, auto&& body) -> int {
-        hipEvent_t e0 = timings ? d.mark() : nullptr;
-        CK(body());
-        hipEvent_t e1 = timings ? d.mark() : nullptr;
-        if (timings && (!e0 || !e1)) return fail("event record failed");
-        if (timings) spans[which].emplace_back(e0, e1);
-        return 0;
-    };
-    const PresenceArgs a{dX, dW, dpn, dps, dcand, dstat, dnit, df, dconv, dH1, dH0, dnext, (int64_t)NP, (int64_t)NP, V, K, 1,
-                         min_iterations, max_iterations, conv_test_freq, tol};
-    CK(timed(1, [&] { return launch_presence(a, cus, d.stream); }));
-    int n_chunks = 0;
-    for (int first = 0; first < B; first += chunk, ++n_chunks) {
+    r.timing = io.timings != nullptr;
+    const PresenceArgs a = r.a = PresenceArgs{dX, dW, dpn, dps, dcand, dstat, dnit, df, dconv, dH1, dH0, dnext, (int64_t)NP, (int64_t)NP, V, K, 1,
+                                              io.min_iterations, io.max_iterations, io.conv_test_freq, io.tol};
+    CK(r.timed(1, [&] { return launch_presence(a, cus, d.stream); }));
+    for (int first = 0; first < B; first += chunk, ++r.n_chunks) {
         const int count = std::min(chunk, B - first);
         // from the device-resident exposures of the observed null fits; a row's trial count is read off the clipped counts
-        CK(timed(0, [&]() -> int {
-            presence_launch_draw(dH0, dW, dX, dpn, dps, dXb, (int64_t)NP, V, K, seed, SALNMF_EPSILON, first, count, d.stream);
+        CK(r.timed(0, [&]() -> int {
+            presence_launch_draw(dH0, dW, dX, dpn, dps, dXb, (int64_t)NP, V, K, io.seed, SALNMF_EPSILON, first, count, d.stream);
             HIPCK(hipGetLastError());
             return 0;
         }));
-        if (draws) HIPCK(hipMemcpyAsync(h_draws.data() + (size_t)first * PV, dXb, (size_t)count * PV * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+        if (io.draws)
+            HIPCK(hipMemcpyAsync(r.h_draws.data() + (size_t)first * PV, dXb, (size_t)count * PV * sizeof(double), hipMemcpyDeviceToHost, d.stream));
         // a draw's problems keep their statistic and iteration counts only
         PresenceArgs c = a;
         c.X = dXb;
@@ -756,62 +826,196 @@ extern "C" int salnmf_signature_presence(int device, const double* counts, int64
         c.stat = dstat_b + (size_t)first * NP;
         c.nit = dnit_b + 2 * (size_t)first * NP;
         c.f = nullptr, c.conv = nullptr, c.H1 = nullptr, c.H0 = nullptr;
-        CK(timed(1, [&] { return launch_presence(c, cus, d.stream); }));
+        CK(r.timed(1, [&] { return launch_presence(c, cus, d.stream); }));
     }
     // gof_reduce_kernel over the pairs: n_exceed counts t_b >= t (false for a NaN on either side), null_mean sums from 0.0 in ascending b
     const GofReduceArgs red{dstat, dstat_b, dexceed, dmean, (int64_t)NP, B};
-    CK(timed(2, [&]() -> int {
+    CK(r.timed(2, [&]() -> int {
         gof_launch_reduce(red, d.stream);
         HIPCK(hipGetLastError());
         return 0;
     }));
-    HIPCK(hipMemcpyAsync(h_stat.data(), dstat, NP * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(h_f.data(), df, 2 * NP * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(h_nit.data(), dnit, 2 * NP * sizeof(int), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(h_conv.data(), dconv, 2 * NP * sizeof(int), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(h_H1.data(), dH1, PK * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(h_H0.data(), dH0, PK * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(h_exceed.data(), dexceed, NP * sizeof(int), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(h_mean.data(), dmean, NP * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(h_stat_b.data(), dstat_b, PB * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(h_nit_b.data(), dnit_b, 2 * PB * sizeof(int), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipStreamSynchronize(d.stream));
+    HIPCK(hipMemcpyAsync(r.h_stat.data(), dstat, NP * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(r.h_f.data(), df, 2 * NP * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(r.h_nit.data(), dnit, 2 * NP * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(r.h_conv.data(), dconv, 2 * NP * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(r.h_H1.data(), dH1, PK * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(r.h_H0.data(), dH0, PK * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(r.h_exceed.data(), dexceed, NP * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(r.h_mean.data(), dmean, NP * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(r.h_stat_b.data(), dstat_b, PB * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(r.h_nit_b.data(), dnit_b, 2 * PB * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    return 0;
+}
 
-    // the compact pair list back into the (N, S) results; a sample's alternative fit is that of its first tested pair (every
-    // tested pair of a sample solves the same problem on C and holds the same bits)
+// Waits for the stream, then the compact pair list back into the (N, S) results and the first four timings.
+int presence_finish(const PresenceIO& io, PresenceRun& r) {
+    const int V = io.V, K = io.K, B = io.B;
+    const size_t NP = r.NP, NS = (size_t)io.N * io.S;
+    HIPCK(hipStreamSynchronize(r.d->stream));
+    // a sample's alternative fit is that of its first tested pair (every tested pair of a sample solves the same problem on C and
+    // holds the same bits)
     for (size_t j = 0; j < NP; ++j) {
-        const size_t o = slot[j], n = (size_t)pair_n[j];
-        statistic[o] = h_stat[j];
-        n_exceed[o] = h_exceed[j];
-        null_mean[o] = h_mean[j];
-        null_errors[o] = h_f[2 * j + 1];
-        std::copy(h_H0.begin() + j * K, h_H0.begin() + (j + 1) * K, null_exposures + o * K);
-        for (int i = 0; i < 2; ++i) n_iterations[2 * o + i] = h_nit[2 * j + i], converged[2 * o + i] = h_conv[2 * j + i];
-        if (j == 0 || (size_t)pair_n[j - 1] != n) {
-            std::copy(h_H1.begin() + j * K, h_H1.begin() + (j + 1) * K, exposures + n * K);
-            errors[n] = h_f[2 * j];
+        const size_t o = r.slot[j], n = (size_t)r.pair_n[j];
+        io.statistic[o] = r.h_stat[j];
+        io.n_exceed[o] = r.h_exceed[j];
+        io.null_mean[o] = r.h_mean[j];
+        io.null_errors[o] = r.h_f[2 * j + 1];
+        std::copy(r.h_H0.begin() + j * K, r.h_H0.begin() + (j + 1) * K, io.null_exposures + o * K);
+        for (int i = 0; i < 2; ++i) io.n_iterations[2 * o + i] = r.h_nit[2 * j + i], io.converged[2 * o + i] = r.h_conv[2 * j + i];
+        if (j == 0 || (size_t)r.pair_n[j - 1] != n) {
+            std::copy(r.h_H1.begin() + j * K, r.h_H1.begin() + (j + 1) * K, io.exposures + n * K);
+            io.errors[n] = r.h_f[2 * j];
         }
         for (size_t b = 0; b < (size_t)B; ++b) {
-            null_statistics[b * NS + o] = h_stat_b[b * NP + j];
-            for (int i = 0; i < 2; ++i) null_n_iterations[2 * (b * NS + o) + i] = h_nit_b[2 * (b * NP + j) + i];
-            if (draws)  // plain counts: the clipped zeros restored to 0
+            io.null_statistics[b * NS + o] = r.h_stat_b[b * NP + j];
+            for (int i = 0; i < 2; ++i) io.null_n_iterations[2 * (b * NS + o) + i] = r.h_nit_b[2 * (b * NP + j) + i];
+            if (io.draws)  // plain counts: the clipped zeros restored to 0
                 for (int v = 0; v < V; ++v) {
-                    const double c = h_draws[(b * NP + j) * V + v];
-                    draws[(b * NS + o) * V + v] = c < 1.0 ? 0.0 : c;
+                    const double c = r.h_draws[(b * NP + j) * V + v];
+                    io.draws[(b * NS + o) * V + v] = c < 1.0 ? 0.0 : c;
+                }
+        }
+    }
+    if (io.timings) {
+        for (int i = 0; i < 3; ++i) CK(r.span_ms(i, io.timings + i));
+        io.timings[3] = (double)r.n_chunks;
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int salnmf_signature_presence(int device, const double* counts, int64_t n_samples, int n_features, const double* signatures, int n_signatures,
+                                         const int* test, int n_test, const uint8_t* candidates, int n_draws, uint64_t seed, int min_iterations,
+                                         int max_iterations, int conv_test_freq, double tol, int64_t chunk_bytes, uint8_t* tested, double* statistic,
+                                         int* n_exceed, double* null_mean, double* exposures, double* errors, double* null_exposures, double* null_errors,
+                                         int* n_iterations, int* converged, double* null_statistics, int* null_n_iterations, double* draws,
+                                         double* timings) {
+    const PresenceIO io{device, counts, n_samples, n_features, signatures, n_signatures, test, n_test, candidates, n_draws, seed, min_iterations,
+                        max_iterations, conv_test_freq, tol, chunk_bytes, tested, statistic, n_exceed, null_mean, exposures, errors, null_exposures,
+                        null_errors, n_iterations, converged, null_statistics, null_n_iterations, draws, timings};
+    PresenceRun r;
+    CK(presence_enqueue(io, 0, r));
+    if (r.NP == 0) return 0;
+    return presence_finish(io, r);
+}
+
+// ---- the presence test's power: the tested signature planted at given shares of the null fit (salnmf_power.h)
+
+extern "C" int salnmf_signature_power(int device, const double* counts, int64_t n_samples, int n_features, const double* signatures, int n_signatures,
+                                      const int* test, int n_test, const uint8_t* candidates, int n_draws, uint64_t seed, int min_iterations,
+                                      int max_iterations, int conv_test_freq, double tol, int64_t chunk_bytes, const double* shares, int n_shares,
+                                      int n_alt_draws, int max_exceed, uint8_t* tested, double* statistic, int* n_exceed, double* null_mean,
+                                      double* exposures, double* errors, double* null_exposures, double* null_errors, int* n_iterations, int* converged,
+                                      double* null_statistics, int* null_n_iterations, double* draws, double* planted_exposures, double* alt_statistics,
+                                      int* alt_n_iterations, int* alt_n_exceed, int* n_detected, double* alt_mean, double* alt_draws, double* timings) {
+    const int L = n_shares, A = n_alt_draws, B = n_draws;
+    if (!shares || !planted_exposures || !alt_statistics || !alt_n_iterations || !alt_n_exceed || !n_detected || !alt_mean) return fail("null argument");
+    CK(gof_check_draws(B));
+    if (L < 1 || L > POWER_MAX_SHARES) return fail("n_shares must be in [1, %d], got %d", POWER_MAX_SHARES, L);
+    for (int l = 0; l < L; ++l) {
+        if (!std::isfinite(shares[l]) || shares[l] < 0.0 || shares[l] >= 1.0) return fail("share %d must be finite and in [0, 1), got %g", l, shares[l]);
+        if (l > 0 && !(shares[l] > shares[l - 1])) return fail("shares must be strictly ascending: share %d is %g after %g", l, shares[l], shares[l - 1]);
+    }
+    if (A < 1 || A > POWER_MAX_DRAWS) return fail("n_alt_draws must be in [1, %d], got %d", POWER_MAX_DRAWS, A);
+    if (max_exceed < 0 || max_exceed > B) return fail("max_exceed must be in [0, %d], got %d", B, max_exceed);
+    const int64_t R = (int64_t)L * A;  // rows r = l A + a
+    const PresenceIO io{device, counts, n_samples, n_features, signatures, n_signatures, test, n_test, candidates, n_draws, seed, min_iterations,
+                        max_iterations, conv_test_freq, tol, chunk_bytes, tested, statistic, n_exceed, null_mean, exposures, errors, null_exposures,
+                        null_errors, n_iterations, converged, null_statistics, null_n_iterations, draws, timings};
+    std::vector<double> h_Hp, h_stat_a, h_mean_a, h_draws_a;  // (before r: they outlive the copies into them, which r.d waits for)
+    std::vector<int> h_nit_a, h_exceed_a, h_ndet;
+    PresenceRun r;
+    CK(presence_enqueue(io, R, r));
+    const int64_t N = n_samples;
+    const int V = n_features, K = n_signatures, S = n_test;
+    const size_t NS = (size_t)N * S, NP = r.NP;
+    const double nan = std::nan("");
+    std::fill(planted_exposures, planted_exposures + (size_t)L * NS * K, nan);
+    std::fill(alt_statistics, alt_statistics + (size_t)R * NS, nan);
+    std::fill(alt_mean, alt_mean + (size_t)L * NS, nan);
+    std::fill(alt_n_iterations, alt_n_iterations + 2 * (size_t)R * NS, 0);
+    std::fill(alt_n_exceed, alt_n_exceed + (size_t)R * NS, 0);
+    std::fill(n_detected, n_detected + (size_t)L * NS, 0);
+    if (alt_draws) std::fill(alt_draws, alt_draws + (size_t)R * NS * V, 0.0);
+    if (timings) timings[4] = timings[5] = timings[6] = timings[7] = timings[8] = 0.0;
+    if (NP == 0) return 0;
+
+    const size_t PV = NP * V, PK = NP * K;
+    DevBufs& d = *r.d;
+    h_Hp.resize((size_t)L * PK), h_stat_a.resize((size_t)R * NP), h_mean_a.resize((size_t)L * NP), h_draws_a.resize(alt_draws ? (size_t)R * PV : 0);
+    h_nit_a.resize(2 * (size_t)R * NP), h_exceed_a.resize((size_t)R * NP), h_ndet.resize((size_t)L * NP);
+    double* dshares = d.get<double>((size_t)L);
+    double* dHp = d.get<double>((size_t)L * PK);
+    double* dstat_a = d.get<double>((size_t)R * NP);
+    int* dnit_a = d.get<int>(2 * (size_t)R * NP);
+    int* dexceed_a = d.get<int>((size_t)R * NP);
+    int* dndet = d.get<int>((size_t)L * NP);
+    double* dmean_a = d.get<double>((size_t)L * NP);
+    if (!dshares || !dHp || !dstat_a || !dnit_a || !dexceed_a || !dndet || !dmean_a)
+        return fail("hipMalloc failed (%d shares x %d draws of %zu pairs x %d, %d signatures)", L, A, NP, V, K);
+    HIPCK(hipMemcpyAsync(dshares, shares, (size_t)L * sizeof(double), hipMemcpyHostToDevice, d.stream));
+    CK(r.timed(3, [&]() -> int {
+        power_launch_plant(PowerPlantArgs{r.dH0, r.dps, dshares, dHp, (int64_t)NP, K, L}, d.stream);
+        HIPCK(hipGetLastError());
+        return 0;
+    }));
+    // rows per chunk: the presence test's buffer and rule
+    const int64_t chunk = std::min<int64_t>(R, r.chunk_rows);
+    int n_chunks = 0;
+    for (int64_t first = 0; first < R; first += chunk, ++n_chunks) {
+        const int64_t count = std::min(chunk, R - first);
+        CK(r.timed(4, [&]() -> int {
+            power_launch_draw(dHp, r.dW, r.dX, r.dpn, r.dps, r.dXb, (int64_t)NP, V, K, seed, SALNMF_EPSILON, A, first, count, d.stream);
+            HIPCK(hipGetLastError());
+            return 0;
+        }));
+        if (alt_draws)
+            HIPCK(hipMemcpyAsync(h_draws_a.data() + (size_t)first * PV, r.dXb, (size_t)count * PV * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+        PresenceArgs c = r.a;  // as a null draw's launch
+        c.X = r.dXb;
+        c.by_sample = 0;
+        c.P = count * (int64_t)NP;
+        c.stat = dstat_a + (size_t)first * NP;
+        c.nit = dnit_a + 2 * (size_t)first * NP;
+        c.f = nullptr, c.conv = nullptr, c.H1 = nullptr, c.H0 = nullptr;
+        CK(r.timed(5, [&] { return launch_presence(c, r.in.cus, d.stream); }));
+    }
+    CK(r.timed(6, [&]() -> int {
+        power_launch_reduce(PowerReduceArgs{r.dstat_b, dstat_a, dexceed_a, dndet, dmean_a, (int64_t)NP, B, L, A, max_exceed}, d.stream);
+        HIPCK(hipGetLastError());
+        return 0;
+    }));
+    HIPCK(hipMemcpyAsync(h_Hp.data(), dHp, h_Hp.size() * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(h_stat_a.data(), dstat_a, h_stat_a.size() * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(h_nit_a.data(), dnit_a, h_nit_a.size() * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(h_exceed_a.data(), dexceed_a, h_exceed_a.size() * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(h_ndet.data(), dndet, h_ndet.size() * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(h_mean_a.data(), dmean_a, h_mean_a.size() * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    CK(presence_finish(io, r));  // waits for the stream
+
+    for (size_t j = 0; j < NP; ++j) {
+        const size_t o = r.slot[j];
+        for (size_t l = 0; l < (size_t)L; ++l) {
+            std::copy(h_Hp.begin() + (l * NP + j) * K, h_Hp.begin() + (l * NP + j + 1) * K, planted_exposures + (l * NS + o) * K);
+            n_detected[l * NS + o] = h_ndet[l * NP + j];
+            alt_mean[l * NS + o] = h_mean_a[l * NP + j];
+        }
+        for (size_t q = 0; q < (size_t)R; ++q) {
+            alt_statistics[q * NS + o] = h_stat_a[q * NP + j];
+            alt_n_exceed[q * NS + o] = h_exceed_a[q * NP + j];
+            for (int i = 0; i < 2; ++i) alt_n_iterations[2 * (q * NS + o) + i] = h_nit_a[2 * (q * NP + j) + i];
+            if (alt_draws)  // plain counts: the clipped zeros restored to 0
+                for (int v = 0; v < V; ++v) {
+                    const double c = h_draws_a[(q * NP + j) * V + v];
+                    alt_draws[(q * NS + o) * V + v] = c < 1.0 ? 0.0 : c;
                 }
         }
     }
     if (timings) {
-        for (int i = 0; i < 3; ++i) {
-            double total = 0.0;
-            for (const auto& pr : spans[i]) {
-                float ms = 0.f;
-                HIPCK(hipEventElapsedTime(&ms, pr.first, pr.second));
-                total += (double)ms;
-            }
-            timings[i] = total;
-        }
-        timings[3] = (double)n_chunks;
+        for (int i = 3; i < 7; ++i) CK(r.span_ms(i, timings + i + 1));
+        timings[8] = (double)n_chunks;
     }
     return 0;
 }

@@ -58,6 +58,49 @@ def check_test(test, K: int) -> np.ndarray:
     return np.array([int(v) for v in values], dtype=np.int32)
 
 
+def check_presence_arguments(counts, signatures, test, n_draws, seed, candidates, min_iterations, max_iterations, conv_test_freq, tol, chunk_bytes):
+    """What :func:`signature_presence_test` checks before it touches a device ->
+    ``(X, W, T, C, B, seed, min_it, max_it, freq, tol, chunk)``."""
+    X, W, _, seed, min_it, max_it, freq, tol, _, chunk = check_arguments(counts, signatures, 0, seed, (), min_iterations, max_iterations,
+                                                                        conv_test_freq, tol, chunk_bytes)
+    if max_it % freq != 0:
+        raise ValueError("'max_iterations' must be a multiple of 'conv_test_freq': the two solves of a pair follow one another on the device.")
+    check_integer_counts(X)
+    B = check_n_draws(n_draws)
+    T = check_test(test, W.shape[0])
+    C, _, _ = check_sets(candidates, None, False, X.shape[0], W.shape[0])
+    return X, W, T, C, B, seed, min_it, max_it, freq, tol, chunk
+
+
+class PresenceOutputs:
+    """The arrays ``salnmf_signature_presence`` fills, in the C order, and the :class:`PresenceResult` made of them."""
+
+    def __init__(self, N, V, K, S, B, keep_draws):
+        f64 = lambda *shape: np.empty(shape, dtype=np.float64)  # noqa: E731
+        i32 = lambda *shape: np.empty(shape, dtype=np.int32)  # noqa: E731
+        self.B = B
+        self.tested = np.zeros((N, S), dtype=np.uint8)
+        self.stat, self.mean, self.H, self.err, self.H0, self.err0 = f64(N, S), f64(N, S), f64(N, K), f64(N), f64(N, S, K), f64(N, S)
+        self.exceed, self.nit, self.conv = i32(N, S), i32(N, S, 2), i32(N, S, 2)
+        self.stat_b, self.nit_b = f64(B, N, S), i32(B, N, S, 2)
+        self.drawn = f64(B, N, S, V) if keep_draws else None
+
+    def pointers(self):
+        p = _lib.pointer
+        return (p(self.tested), p(self.stat), p(self.exceed), p(self.mean), p(self.H), p(self.err), p(self.H0), p(self.err0), p(self.nit),
+                p(self.conv), p(self.stat_b), p(self.nit_b), p(self.drawn))
+
+    def result(self, T, C, ms, total_s) -> PresenceResult:
+        tested = self.tested.astype(bool)
+        timings = {"draw_s": ms[0] / 1e3, "solve_s": ms[1] / 1e3, "reduce_s": ms[2] / 1e3, "presence_kernel_ms": ms[1], "n_chunks": int(ms[3]),
+                   "total_s": total_s}
+        p_value = np.where(tested, (1 + self.exceed.astype(np.int64)) / (self.B + 1), np.nan)
+        return PresenceResult(statistic=self.stat, p_value=p_value, n_exceed=self.exceed, tested=tested, exposures=self.H, reconstruction_errors=self.err,
+                              null_exposures=self.H0, null_errors=self.err0, null_statistics=self.stat_b, null_mean=self.mean, n_iterations=self.nit,
+                              converged=self.conv.astype(bool), null_n_iterations=self.nit_b, test=tuple(int(v) for v in T), candidates=C,
+                              draws=self.drawn, timings=timings)
+
+
 def signature_presence_test(counts, signatures, test, n_draws: int = 200, seed: int = 0, candidates=None, min_iterations: int = 500,
                             max_iterations: int = 10000, conv_test_freq: int = 10, tol: float = 1e-7, chunk_bytes: int | None = None,
                             keep_draws: bool = False, device: int = 0) -> PresenceResult:
@@ -75,37 +118,15 @@ def signature_presence_test(counts, signatures, test, n_draws: int = 200, seed: 
     The counts are non-negative integers with row totals below 2**32; anything out of range is a ``ValueError`` before the
     device is touched."""
     t_start = time.perf_counter()
-    X, W, _, seed, min_it, max_it, freq, tol, _, chunk = check_arguments(counts, signatures, 0, seed, (), min_iterations, max_iterations,
-                                                                        conv_test_freq, tol, chunk_bytes)
-    if max_it % freq != 0:
-        raise ValueError("'max_iterations' must be a multiple of 'conv_test_freq': the two solves of a pair follow one another on the device.")
-    check_integer_counts(X)
-    B = check_n_draws(n_draws)
-    (N, V), K = X.shape, W.shape[0]
-    T = check_test(test, K)
-    S = int(T.size)
-    C, _, _ = check_sets(candidates, None, False, N, K)
+    X, W, T, C, B, seed, min_it, max_it, freq, tol, chunk = check_presence_arguments(counts, signatures, test, n_draws, seed, candidates, min_iterations,
+                                                                                     max_iterations, conv_test_freq, tol, chunk_bytes)
+    (N, V), K, S = X.shape, W.shape[0], int(T.size)
     lib = _lib.load_with_device()
-
-    f64 = lambda *shape: np.empty(shape, dtype=np.float64)  # noqa: E731
-    i32 = lambda *shape: np.empty(shape, dtype=np.int32)  # noqa: E731
-    tested = np.zeros((N, S), dtype=np.uint8)
-    stat, mean, H, err, H0, err0 = f64(N, S), f64(N, S), f64(N, K), f64(N), f64(N, S, K), f64(N, S)
-    exceed, nit, conv = i32(N, S), i32(N, S, 2), i32(N, S, 2)
-    stat_b, nit_b = f64(B, N, S), i32(B, N, S, 2)
-    drawn = f64(B, N, S, V) if keep_draws else None
+    out = PresenceOutputs(N, V, K, S, B, keep_draws)
     Cb = None if C is None else C.astype(np.uint8)
     ms = (c_double * 4)()
     p = _lib.pointer
     _lib.check(lib.salnmf_signature_presence(
-        int(device), p(X), N, V, p(W), K, p(T), S, p(Cb), B, seed, min_it, max_it, freq, tol, chunk,
-        p(tested), p(stat), p(exceed), p(mean), p(H), p(err), p(H0), p(err0), p(nit), p(conv), p(stat_b), p(nit_b), p(drawn),
-        ctypes.cast(ms, _lib._D),
+        int(device), p(X), N, V, p(W), K, p(T), S, p(Cb), B, seed, min_it, max_it, freq, tol, chunk, *out.pointers(), ctypes.cast(ms, _lib._D),
     ))
-    tested = tested.astype(bool)
-    timings = {"draw_s": ms[0] / 1e3, "solve_s": ms[1] / 1e3, "reduce_s": ms[2] / 1e3, "presence_kernel_ms": ms[1], "n_chunks": int(ms[3]),
-               "total_s": time.perf_counter() - t_start}
-    p_value = np.where(tested, (1 + exceed.astype(np.int64)) / (B + 1), np.nan)
-    return PresenceResult(statistic=stat, p_value=p_value, n_exceed=exceed, tested=tested, exposures=H, reconstruction_errors=err, null_exposures=H0,
-                          null_errors=err0, null_statistics=stat_b, null_mean=mean, n_iterations=nit, converged=conv.astype(bool),
-                          null_n_iterations=nit_b, test=tuple(int(v) for v in T), candidates=C, draws=drawn, timings=timings)
+    return out.result(T, C, ms, time.perf_counter() - t_start)
