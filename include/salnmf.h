@@ -739,6 +739,56 @@ int salnmf_signature_power(int device, const double* counts, int64_t n_samples, 
                            double* planted_exposures, double* alt_statistics, int* alt_n_iterations, int* alt_n_exceed,
                            int* n_detected, double* alt_mean, double* alt_draws, double* timings);
 
+/* ---- How far can one exposure move before the sample's fit degrades?  The profile likelihood of h_s per (sample, tested
+ * signature), and the confidence interval it gives (csrc/salnmf_profile.h).  counts, signatures, test,
+ * candidates, the iteration arguments and max_iterations % conv_test_freq == 0 as salnmf_signature_presence, except that the
+ * counts need not be integers: nothing is drawn.  Contract, for sample n with set C_n, s = test[j] and a value c >= 0:
+ *   the pair is tested or UNTESTED by salnmf_signature_presence's rule, and its alternative fit (h1, f1: exposures, errors) is
+ *   that call's, bit for bit -- the observed launch is the same;
+ *   the FROZEN SOLVE at c starts from h_s = c, h_k = (sum_v x_v) / (|C_n| - 1) on C_n \ {s} and exactly 0.0 off C_n; every step
+ *   applies the refit's update factors with the SALNMF_EPSILON clip to the members of C_n \ {s} only, h_s is never touched; the
+ *   objective is the sample's KL divergence at the whole h, the stop rule the refit's.  Its error is f(c), and g(c) = f(c) - f1
+ *   (one rounded subtraction).  At c = 0.0 it is bit for bit salnmf_signature_presence's null solve and g(0) its statistic.
+ * salnmf_profile_likelihood evaluates g on given values: values holds n_values doubles used for every pair (values_per_pair
+ * = 0) or n_samples x n_test x n_values (values_per_pair = 1), n_values in [1, 4096], every one finite and >= 0; every solve
+ * starts cold, so an entry depends on its pair and its value only.  Outputs: tested  n_samples x n_test;  profile (g),
+ * profile_errors (f), n_iterations, converged  n_samples x n_test x n_values;  profile_exposures  NULL, or the same x
+ * n_signatures (entry s exactly c, exactly 0.0 off C_n);  exposures  n_samples x n_signatures and errors  n_samples.  Entries of
+ * an untested pair: NaN in the doubles, 0 in the integers.  timings: NULL, or 3 doubles -- milliseconds by device events of the
+ * observed launch and of the profile launch, and the number of device problems (a pair's values go in runs of 8).
+ * Refused on the host before any launch, status 1 and salnmf_last_error: what salnmf_signature_presence refuses of these
+ * arguments; n_values outside [1, 4096]; values_per_pair not 0 or 1; a value that is not finite or is negative. */
+int salnmf_profile_likelihood(int device, const double* counts, int64_t n_samples, int n_features, const double* signatures,
+                              int n_signatures, const int* test, int n_test, const uint8_t* candidates, const double* values,
+                              int n_values, int values_per_pair, int min_iterations, int max_iterations, int conv_test_freq,
+                              double tol, uint8_t* tested, double* profile, double* profile_errors, int* n_iterations,
+                              int* converged, double* profile_exposures, double* exposures, double* errors, double* timings);
+
+/* salnmf_exposure_intervals searches the two ends of { c : g(c) <= max_kl_increase } on the device, every trial a frozen solve
+ * from a cold start and all search arithmetic in fp64; a comparison with a NaN is false.  With hh = h1[s], D = max_kl_increase,
+ * J = n_bisections, E = max_expansions and g0 = statistic[n, j] = g(0):
+ *   lower end: g0 <= D gives exactly 0.0 without a trial.  Otherwise lo = 0.0, hi = hh; J times m = 0.5 (lo + hi), g(m) > D ?
+ *   lo = m : hi = m.  While lo is still 0.0 after them (the root lies below hh / 2^J) the halving goes on, at most E more
+ *   times, and stops at the first trial with g(m) > D; lower = lo.  So lower == 0.0 with g0 > D only if none of J + E halvings
+ *   of [0, hh] found a value outside.
+ *   upper end: d = hh > 1.0 ? hh : 1.0, lo = hh; expansion trial e = 0, 1, .. is c = hh + d 2^e; g(c) > D ? hi = c and the
+ *   expansion stops : lo = c.  After E trials without a bracket upper = +inf, bracketed = 0, no bisection.  Otherwise J times
+ *   m = 0.5 (lo + hi), g(m) > D ? hi = m : lo = m; upper = hi.
+ * Both ends are the outer ends of their last bracket: the interval returned contains the exact one.  lower == 0.0, that is g0 <= D,
+ * is the criterion on which salnmf_assign_signatures removes a signature at max_kl_increase = D.
+ * Outputs, n_samples x n_test: tested, lower, upper, estimate (hh), bracketed (1 / 0), statistic (g0), null_errors (f(0));
+ * n_trials  the same x 2 (lower, upper);  exposures, errors as above;  trace_values, trace_profile  both NULL, or n_samples x
+ * n_test x 2 x (E + J): the trial values and their g in trial order, NaN past n_trials.  Entries of an untested pair: NaN in the
+ * doubles, 0 elsewhere.  timings as above (a problem is one end of one pair).
+ * Refused on the host before any launch: what salnmf_profile_likelihood refuses of the shared arguments; max_kl_increase not
+ * finite or negative; n_bisections outside [0, 64]; max_expansions outside [1, 1000]; one trace output without the other. */
+int salnmf_exposure_intervals(int device, const double* counts, int64_t n_samples, int n_features, const double* signatures,
+                              int n_signatures, const int* test, int n_test, const uint8_t* candidates, double max_kl_increase,
+                              int n_bisections, int max_expansions, int min_iterations, int max_iterations, int conv_test_freq,
+                              double tol, uint8_t* tested, double* lower, double* upper, double* estimate, uint8_t* bracketed,
+                              int* n_trials, double* statistic, double* null_errors, double* exposures, double* errors,
+                              double* trace_values, double* trace_profile, double* timings);
+
 #ifdef __cplusplus
 }
 #endif

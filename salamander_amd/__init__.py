@@ -12,6 +12,7 @@ from .anndata_compat import AnnData, MuData
 from .assign import AssignResult, assign_signatures
 from .engine import Engine
 from .gof import GofResult, draw_model_counts, goodness_of_fit
+from .intervals import IntervalResult, ProfileResult, exposure_intervals, profile_likelihood
 from .power import PowerResult, signature_power
 from .presence import PresenceResult, signature_presence_test
 from .refit import RefitResult, refit_exposures
@@ -22,4 +23,4 @@ from .stability import signature_stability
 __version__ = "0.1.0"
 __all__ = ["models", "Engine", "AnnData", "MuData", "EngineUnavailable", "resample_counts", "signature_stability", "refit_exposures", "RefitResult", "assign_signatures",
            "AssignResult", "split_counts", "goodness_of_fit", "draw_model_counts", "GofResult", "signature_presence_test",
-           "PresenceResult", "signature_power", "PowerResult"]
+           "PresenceResult", "signature_power", "PowerResult", "profile_likelihood", "ProfileResult", "exposure_intervals", "IntervalResult"]

@@ -150,6 +150,11 @@ SIGNATURES = {
     "salnmf_signature_power": (c_int, [c_int, _D, c_int64, c_int, _D, c_int, _I, c_int, POINTER(c_uint8), c_int, c_uint64, c_int, c_int, c_int,
                                        c_double, c_int64, _D, c_int, c_int, c_int, POINTER(c_uint8), _D, _I, _D, _D, _D, _D, _D, _I, _I, _D, _I, _D,
                                        _D, _D, _I, _I, _I, _D, _D, _D]),
+    # the profile likelihood of one exposure and its interval: salamander_amd/intervals.py
+    "salnmf_profile_likelihood": (c_int, [c_int, _D, c_int64, c_int, _D, c_int, _I, c_int, POINTER(c_uint8), _D, c_int, c_int, c_int, c_int, c_int,
+                                          c_double, POINTER(c_uint8), _D, _D, _I, _I, _D, _D, _D, _D]),
+    "salnmf_exposure_intervals": (c_int, [c_int, _D, c_int64, c_int, _D, c_int, _I, c_int, POINTER(c_uint8), c_double, c_int, c_int, c_int, c_int, c_int,
+                                          c_double, POINTER(c_uint8), _D, _D, _D, POINTER(c_uint8), _I, _D, _D, _D, _D, _D, _D, _D]),
 }
 
 OBJECTIVE_SLOTS = 256  # SALNMF_OBJECTIVE_SLOTS

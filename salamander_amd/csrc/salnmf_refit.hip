@@ -4,7 +4,9 @@
 // and 14.1; and of the goodness-of-fit test built on it (salnmf_draw_model_counts, salnmf_goodness_of_fit; salnmf_gof.h:
 // model_draw_kernel, gof_reduce_kernel, which salnmf_batch.hip compiles); and of the signature-presence test
 // (salnmf_signature_presence; salnmf_presence.h: presence_kernel here, presence_draw_kernel in salnmf_batch.hip), DESIGN.md section 17;
-// and of that test's power analysis (salnmf_signature_power; salnmf_power.h: its three kernels in salnmf_batch.hip), DESIGN.md section 18.
+// and of that test's power analysis (salnmf_signature_power; salnmf_power.h: its three kernels in salnmf_batch.hip), DESIGN.md section 18;
+// and of the profile likelihood of one exposure and its interval (salnmf_profile_likelihood, salnmf_exposure_intervals;
+// salnmf_profile.h: profile_kernel), DESIGN.md section 19.
 #define SALNMF_TEMPLATES_ONLY 1
 #define SALNMF_REFIT_KERNELS 1
 #include "../../include/salnmf.h"
@@ -15,6 +17,7 @@
 #include "salnmf_gof.h"
 #include "salnmf_presence.h"
 #include "salnmf_power.h"
+#include "salnmf_profile.h"
 
 #include <algorithm>
 #include <cmath>
@@ -166,6 +169,23 @@ int launch_presence(const PresenceArgs& a, int cus, hipStream_t stream) {
         case 5: hipLaunchKernelGGL(presence_kernel<5>, grid, dim3(BLOCK), 0, stream, a); break;
         case 6: hipLaunchKernelGGL(presence_kernel<6>, grid, dim3(BLOCK), 0, stream, a); break;
         default: return fail("no presence kernel for %d signatures", a.K);
+    }
+    HIPCK(hipGetLastError());
+    return 0;
+}
+
+int launch_profile(const ProfileArgs& a, int cus, hipStream_t stream) {
+    const int64_t ntiles = (a.P + 15) / 16;
+    const dim3 grid((unsigned)std::min<int64_t>((int64_t)cus, (ntiles + WAVES - 1) / WAVES));  // as launch_refit
+    HIPCK(hipMemsetAsync(a.next_tile, 0, sizeof(unsigned), stream));
+    switch ((a.K + 15) / 16) {
+        case 1: hipLaunchKernelGGL(profile_kernel<1>, grid, dim3(BLOCK), 0, stream, a); break;
+        case 2: hipLaunchKernelGGL(profile_kernel<2>, grid, dim3(BLOCK), 0, stream, a); break;
+        case 3: hipLaunchKernelGGL(profile_kernel<3>, grid, dim3(BLOCK), 0, stream, a); break;
+        case 4: hipLaunchKernelGGL(profile_kernel<4>, grid, dim3(BLOCK), 0, stream, a); break;
+        case 5: hipLaunchKernelGGL(profile_kernel<5>, grid, dim3(BLOCK), 0, stream, a); break;
+        case 6: hipLaunchKernelGGL(profile_kernel<6>, grid, dim3(BLOCK), 0, stream, a); break;
+        default: return fail("no profile kernel for %d signatures", a.K);
     }
     HIPCK(hipGetLastError());
     return 0;
@@ -701,6 +721,35 @@ struct PresenceRun {
     }
 };
 
+int presence_check_test(const int* test, int S, int K) {
+    if (S < 1 || S > REFIT_KMAX) return fail("n_test must be in [1, %d], got %d", REFIT_KMAX, S);
+    for (int j = 0; j < S; ++j) {
+        if (test[j] < 0 || test[j] >= K) return fail("tested signature %d is not in [0, %d)", test[j], K);
+        for (int i = 0; i < j; ++i)
+            if (test[i] == test[j]) return fail("signature %d is tested twice", test[j]);
+    }
+    return 0;
+}
+
+// The tested pairs, sample after sample: s is a candidate and not the only one.  Pair j is entry slot[j] of the (N, S) results.
+void presence_list_pairs(const RefitInputs& in, int64_t N, int K, const int* test, int S, bool with_candidates, uint8_t* tested, std::vector<int>& pair_n,
+                         std::vector<int>& pair_s, std::vector<size_t>& slot) {
+    const int words = ((K + 15) / 16 + 1) / 2;
+    for (int64_t n = 0; n < N; ++n) {
+        int size = K;
+        if (with_candidates) {
+            size = 0;
+            for (int w = 0; w < words; ++w) size += __builtin_popcount(in.cand[(size_t)n * words + w]);
+        }
+        for (int j = 0; j < S; ++j) {
+            const int s = test[j];
+            const bool member = !with_candidates || ((in.cand[(size_t)n * words + (s >> 5)] >> (s & 31)) & 1u);
+            tested[(size_t)n * S + j] = member && size > 1;
+            if (member && size > 1) pair_n.push_back((int)n), pair_s.push_back(s), slot.push_back((size_t)n * S + j);
+        }
+    }
+}
+
 // Validation, the pair list, the untested entries of the results, and -- with a tested pair -- everything the presence test puts
 // on the stream: the uploads, the observed launch, the null chunks, the reduction and the downloads.  Nothing is waited for.  h0
 // (r.dH0, [pairs][K]) and the null statistics (r.dstat_b, [B][pairs]) stay on the device; the chunk buffer r.dXb holds
@@ -717,35 +766,16 @@ int presence_enqueue(const PresenceIO& io, int64_t other_rows, PresenceRun& r) {
     CK(gof_check_draws(B));
     if (io.conv_test_freq >= 1 && io.max_iterations >= 0 && io.max_iterations % io.conv_test_freq != 0)
         return fail("max_iterations must be a multiple of conv_test_freq, got %d and %d", io.max_iterations, io.conv_test_freq);
-    if (S < 1 || S > REFIT_KMAX) return fail("n_test must be in [1, %d], got %d", REFIT_KMAX, S);
-    for (int j = 0; j < S; ++j) {
-        if (test[j] < 0 || test[j] >= K) return fail("tested signature %d is not in [0, %d)", test[j], K);
-        for (int i = 0; i < j; ++i)
-            if (test[i] == test[j]) return fail("signature %d is tested twice", test[j]);
-    }
+    CK(presence_check_test(test, S, K));
     RefitInputs& in = r.in;
     CK(refit_prepare(io.device, counts, N, V, io.signatures, K, 0, 0, nullptr, io.min_iterations, io.max_iterations, io.conv_test_freq, io.tol, true, in,
                      AssignSets{candidates, nullptr, 0}));
     CK(refit_check_counts(counts, N, V, in.icounts));  // integer counts, row totals below 2^32 (the values themselves are not used)
     const int cus = in.cus;
-    const int words = ((K + 15) / 16 + 1) / 2;
 
-    // the tested pairs, sample after sample: s is a candidate and not the only one
     const size_t NS = (size_t)N * S, NV = (size_t)N * V, NK = (size_t)N * K;
     std::vector<int>&pair_n = r.pair_n, &pair_s = r.pair_s;
-    for (int64_t n = 0; n < N; ++n) {
-        int size = K;
-        if (candidates) {
-            size = 0;
-            for (int w = 0; w < words; ++w) size += __builtin_popcount(in.cand[(size_t)n * words + w]);
-        }
-        for (int j = 0; j < S; ++j) {
-            const int s = test[j];
-            const bool member = !candidates || ((in.cand[(size_t)n * words + (s >> 5)] >> (s & 31)) & 1u);
-            io.tested[(size_t)n * S + j] = member && size > 1;
-            if (member && size > 1) pair_n.push_back((int)n), pair_s.push_back(s), r.slot.push_back((size_t)n * S + j);
-        }
-    }
+    presence_list_pairs(in, N, K, test, S, candidates != nullptr, io.tested, pair_n, pair_s, r.slot);
     const size_t NP = pair_n.size();
     if (NP > 0x7fffffff) return fail("%zu tested pairs: at most 2^31 - 1", NP);
     const double nan = std::nan("");
@@ -1018,4 +1048,288 @@ extern "C" int salnmf_signature_power(int device, const double* counts, int64_t 
         timings[8] = (double)n_chunks;
     }
     return 0;
+}
+
+// ---- the profile likelihood of one exposure and the interval it gives (salnmf_profile.h).  Both entry
+// points run profile_observed -- the presence test's observed launch, unchanged -- then list their problems on the host, run one
+// profile_kernel launch and scatter its trials.
+
+namespace {
+
+struct ProfileIO {
+    int device;
+    const double* counts;
+    int64_t N;
+    int V;
+    const double* signatures;
+    int K;
+    const int* test;
+    int S;
+    const uint8_t* candidates;
+    int min_iterations, max_iterations, conv_test_freq;
+    double tol;
+    uint8_t* tested;
+    double *exposures, *errors;  // the alternative fit: (N, K) and (N)
+    double* timings;
+};
+
+// The pair list, the observed fits of every pair on the host (stat = f0 - f1, f = (f1, f0), H1) and the device buffers the
+// profile launch reads again.  d is the last member: its destructor waits for the stream before the vectors go.
+struct ProfileRun {
+    RefitInputs in;
+    std::vector<int> pair_n, pair_s;
+    std::vector<size_t> slot;
+    std::vector<double> h_stat, h_f, h_H1;
+    size_t NP = 0;
+    double *dW = nullptr, *dX = nullptr;
+    uint32_t* dcand = nullptr;
+    unsigned* dnext = nullptr;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // around the observed launch, around the profile launch
+    std::unique_ptr<DevBufs> d;
+
+    int launch(const ProfileIO& io, ProfileArgs a) {
+        a.X = dX, a.W = dW, a.cand = dcand, a.next_tile = dnext;
+        a.V = io.V, a.K = io.K, a.min_it = io.min_iterations, a.max_it = io.max_iterations, a.freq = io.conv_test_freq, a.tol = io.tol;
+        ev[2] = io.timings ? d->mark() : nullptr;
+        CK(launch_profile(a, in.cus, d->stream));
+        ev[3] = io.timings ? d->mark() : nullptr;
+        if (io.timings && (!ev[2] || !ev[3])) return fail("event record failed");
+        return 0;
+    }
+    // (after the stream has been waited for)
+    int times(const ProfileIO& io, int64_t P) {
+        if (!io.timings) return 0;
+        float ms = 0.f;
+        HIPCK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        io.timings[0] = (double)ms;
+        HIPCK(hipEventElapsedTime(&ms, ev[2], ev[3]));
+        io.timings[1] = (double)ms;
+        io.timings[2] = (double)P;
+        return 0;
+    }
+};
+
+// Validation, the pair list, the untested entries of the shared results, and -- with a tested pair -- the observed launch of
+// salnmf_signature_presence (the same PresenceArgs: the alternative solve on C, then the null solve, which is the frozen solve
+// at 0.0), waited for and copied back.  The counts need not be integers: nothing is drawn.
+int profile_observed(const ProfileIO& io, ProfileRun& r) {
+    const int64_t N = io.N;
+    const int V = io.V, K = io.K, S = io.S;
+    if (!io.counts || !io.signatures || !io.test || !io.tested || !io.exposures || !io.errors) return fail("null argument");
+    if (io.conv_test_freq >= 1 && io.max_iterations >= 0 && io.max_iterations % io.conv_test_freq != 0)
+        return fail("max_iterations must be a multiple of conv_test_freq, got %d and %d", io.max_iterations, io.conv_test_freq);
+    CK(presence_check_test(io.test, S, K));
+    RefitInputs& in = r.in;
+    CK(refit_prepare(io.device, io.counts, N, V, io.signatures, K, 0, 0, nullptr, io.min_iterations, io.max_iterations, io.conv_test_freq, io.tol, true,
+                     in, AssignSets{io.candidates, nullptr, 0}));
+    presence_list_pairs(in, N, K, io.test, S, io.candidates != nullptr, io.tested, r.pair_n, r.pair_s, r.slot);
+    const size_t NP = r.NP = r.pair_n.size();
+    if (NP > 0x7fffffff) return fail("%zu tested pairs: at most 2^31 - 1", NP);
+    const double nan = std::nan("");
+    std::fill(io.exposures, io.exposures + (size_t)N * K, nan);
+    std::fill(io.errors, io.errors + N, nan);
+    if (io.timings) io.timings[0] = io.timings[1] = io.timings[2] = 0.0;
+    if (NP == 0) return 0;
+
+    const size_t PK = NP * K, NV = (size_t)N * V;
+    r.h_stat.resize(NP), r.h_f.resize(2 * NP), r.h_H1.resize(PK);
+    r.d.reset(new DevBufs);
+    DevBufs& d = *r.d;
+    CK(d.own_stream());
+    double* dW = r.dW = d.get<double>((size_t)K * V);
+    double* dX = r.dX = d.get<double>(NV);
+    int* dpn = d.get<int>(NP);
+    int* dps = d.get<int>(NP);
+    double* dstat = d.get<double>(NP);
+    double* df = d.get<double>(2 * NP);
+    int* dnit = d.get<int>(2 * NP);
+    int* dconv = d.get<int>(2 * NP);
+    double* dH1 = d.get<double>(PK);
+    double* dH0 = d.get<double>(PK);
+    unsigned* dnext = r.dnext = d.get<unsigned>(1);
+    uint32_t* dcand = r.dcand = io.candidates ? d.get<uint32_t>(in.cand.size()) : nullptr;
+    if (!dW || !dX || !dpn || !dps || !dstat || !df || !dnit || !dconv || !dH1 || !dH0 || !dnext || (io.candidates && !dcand))
+        return fail("hipMalloc failed (%zu pairs x %d, %d signatures)", NP, V, K);
+    HIPCK(hipMemcpyAsync(dW, io.signatures, (size_t)K * V * sizeof(double), hipMemcpyHostToDevice, d.stream));
+    HIPCK(hipMemcpyAsync(dX, in.x.data(), NV * sizeof(double), hipMemcpyHostToDevice, d.stream));
+    HIPCK(hipMemcpyAsync(dpn, r.pair_n.data(), NP * sizeof(int), hipMemcpyHostToDevice, d.stream));
+    HIPCK(hipMemcpyAsync(dps, r.pair_s.data(), NP * sizeof(int), hipMemcpyHostToDevice, d.stream));
+    if (dcand) HIPCK(hipMemcpyAsync(dcand, in.cand.data(), in.cand.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+    const PresenceArgs a{dX, dW, dpn, dps, dcand, dstat, dnit, df, dconv, dH1, dH0, dnext, (int64_t)NP, (int64_t)NP, V, K, 1,
+                         io.min_iterations, io.max_iterations, io.conv_test_freq, io.tol};
+    r.ev[0] = io.timings ? d.mark() : nullptr;
+    CK(launch_presence(a, in.cus, d.stream));
+    r.ev[1] = io.timings ? d.mark() : nullptr;
+    if (io.timings && (!r.ev[0] || !r.ev[1])) return fail("event record failed");
+    HIPCK(hipMemcpyAsync(r.h_stat.data(), dstat, NP * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(r.h_f.data(), df, 2 * NP * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(r.h_H1.data(), dH1, PK * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipStreamSynchronize(d.stream));
+    // a sample's alternative fit is that of its first tested pair (presence_finish)
+    for (size_t j = 0; j < NP; ++j)
+        if (j == 0 || r.pair_n[j - 1] != r.pair_n[j]) {
+            const size_t n = (size_t)r.pair_n[j];
+            std::copy(r.h_H1.begin() + j * K, r.h_H1.begin() + (j + 1) * K, io.exposures + n * K);
+            io.errors[n] = r.h_f[2 * j];
+        }
+    return 0;
+}
+
+template <typename T>
+T* profile_upload(DevBufs& d, const std::vector<T>& host) {
+    T* dev = d.get<T>(host.size());
+    if (dev && hipMemcpyAsync(dev, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice, d.stream) != hipSuccess) return nullptr;
+    return dev;
+}
+
+}  // namespace
+
+extern "C" int salnmf_profile_likelihood(int device, const double* counts, int64_t n_samples, int n_features, const double* signatures, int n_signatures,
+                                         const int* test, int n_test, const uint8_t* candidates, const double* values, int n_values, int values_per_pair,
+                                         int min_iterations, int max_iterations, int conv_test_freq, double tol, uint8_t* tested, double* profile,
+                                         double* profile_errors, int* n_iterations, int* converged, double* profile_exposures, double* exposures,
+                                         double* errors, double* timings) {
+    const int64_t N = n_samples;
+    const int K = n_signatures, S = n_test, M = n_values;
+    if (!values || !profile || !profile_errors || !n_iterations || !converged) return fail("null argument");
+    if (M < 1 || M > PROFILE_MAX_VALUES) return fail("n_values must be in [1, %d], got %d", PROFILE_MAX_VALUES, M);
+    if (values_per_pair != 0 && values_per_pair != 1) return fail("values_per_pair must be 0 or 1, got %d", values_per_pair);
+    if (N < 1 || N > 0x7fffffff) return fail("n_samples must be in [1, 2^31), got %lld", (long long)N);
+    if (S < 1 || S > REFIT_KMAX) return fail("n_test must be in [1, %d], got %d", REFIT_KMAX, S);
+    const size_t NS = (size_t)N * S, n_given = values_per_pair ? NS * M : (size_t)M;
+    for (size_t i = 0; i < n_given; ++i)
+        if (!std::isfinite(values[i]) || values[i] < 0.0) return fail("values must be finite and not negative: entry %zu holds %g", i, values[i]);
+    const ProfileIO io{device, counts, N, n_features, signatures, K, test, S, candidates, min_iterations, max_iterations, conv_test_freq, tol, tested,
+                       exposures, errors, timings};
+    // (before r: they outlive the copies into and out of them, which r.d waits for)
+    std::vector<int> prob_n, prob_s, count, h_nit, h_conv;
+    std::vector<double> vals, h_f, h_H;
+    ProfileRun r;
+    CK(profile_observed(io, r));
+    const double nan = std::nan("");
+    std::fill(profile, profile + NS * M, nan);
+    std::fill(profile_errors, profile_errors + NS * M, nan);
+    std::fill(n_iterations, n_iterations + NS * M, 0);
+    std::fill(converged, converged + NS * M, 0);
+    if (profile_exposures) std::fill(profile_exposures, profile_exposures + NS * M * K, nan);
+    const size_t NP = r.NP;
+    if (NP == 0) return 0;
+
+    // a problem is a pair and one run of its values
+    const int T = std::min(M, PROFILE_RUN), runs = (M + T - 1) / T;
+    const size_t P = NP * runs;
+    if (P > 0x7fffffff) return fail("%zu problems (%zu pairs x %d runs of values): at most 2^31 - 1", P, NP, runs);
+    prob_n.resize(P), prob_s.resize(P), count.resize(P), vals.assign(P * T, 0.0);
+    for (size_t j = 0; j < NP; ++j)
+        for (int run = 0; run < runs; ++run) {
+            const size_t p = j * runs + run;
+            prob_n[p] = r.pair_n[j], prob_s[p] = r.pair_s[j], count[p] = std::min(T, M - run * T);
+            const double* from = values + (values_per_pair ? r.slot[j] * M : 0) + (size_t)run * T;
+            std::copy(from, from + count[p], vals.begin() + p * T);
+        }
+    h_f.resize(P * T), h_nit.resize(P * T), h_conv.resize(P * T), h_H.resize(profile_exposures ? P * T * K : 0);
+    DevBufs& d = *r.d;
+    ProfileArgs a{};
+    a.prob_n = profile_upload(d, prob_n), a.prob_s = profile_upload(d, prob_s), a.count = profile_upload(d, count), a.values = profile_upload(d, vals);
+    a.trial_f = d.get<double>(P * T), a.trial_nit = d.get<int>(P * T), a.trial_conv = d.get<int>(P * T);
+    a.trial_H = profile_exposures ? d.get<double>(P * T * K) : nullptr;
+    if (!a.prob_n || !a.prob_s || !a.count || !a.values || !a.trial_f || !a.trial_nit || !a.trial_conv || (profile_exposures && !a.trial_H))
+        return fail("hipMalloc or upload failed (%zu problems of %d values, %d signatures)", P, T, K);
+    a.P = (int64_t)P, a.T = T;
+    CK(r.launch(io, a));
+    HIPCK(hipMemcpyAsync(h_f.data(), a.trial_f, h_f.size() * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(h_nit.data(), a.trial_nit, h_nit.size() * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(h_conv.data(), a.trial_conv, h_conv.size() * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    if (a.trial_H) HIPCK(hipMemcpyAsync(h_H.data(), a.trial_H, h_H.size() * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipStreamSynchronize(d.stream));
+    for (size_t p = 0; p < P; ++p) {
+        const size_t j = p / runs, run = p % runs;
+        const double f1 = r.h_f[2 * j];
+        for (int i = 0; i < count[p]; ++i) {
+            const size_t from = p * T + i, to = r.slot[j] * M + run * T + i;
+            profile[to] = h_f[from] - f1;  // one rounded subtraction, as presence_kernel's statistic
+            profile_errors[to] = h_f[from], n_iterations[to] = h_nit[from], converged[to] = h_conv[from];
+            if (profile_exposures) std::copy(h_H.begin() + from * K, h_H.begin() + (from + 1) * K, profile_exposures + to * K);
+        }
+    }
+    return r.times(io, (int64_t)P);
+}
+
+extern "C" int salnmf_exposure_intervals(int device, const double* counts, int64_t n_samples, int n_features, const double* signatures, int n_signatures,
+                                         const int* test, int n_test, const uint8_t* candidates, double max_kl_increase, int n_bisections,
+                                         int max_expansions, int min_iterations, int max_iterations, int conv_test_freq, double tol, uint8_t* tested,
+                                         double* lower, double* upper, double* estimate, uint8_t* bracketed, int* n_trials, double* statistic,
+                                         double* null_errors, double* exposures, double* errors, double* trace_values, double* trace_profile,
+                                         double* timings) {
+    const int64_t N = n_samples;
+    const int K = n_signatures, S = n_test, J = n_bisections, E = max_expansions;
+    const double delta = max_kl_increase;
+    if (!lower || !upper || !estimate || !bracketed || !n_trials || !statistic || !null_errors || (trace_values == nullptr) != (trace_profile == nullptr))
+        return fail("null argument");
+    if (!std::isfinite(delta) || delta < 0.0) return fail("max_kl_increase must be finite and not negative, got %g", delta);
+    if (J < 0 || J > PROFILE_MAX_BISECTIONS) return fail("n_bisections must be in [0, %d], got %d", PROFILE_MAX_BISECTIONS, J);
+    if (E < 1 || E > PROFILE_MAX_EXPANSIONS) return fail("max_expansions must be in [1, %d], got %d", PROFILE_MAX_EXPANSIONS, E);
+    if (N < 1 || N > 0x7fffffff) return fail("n_samples must be in [1, 2^31), got %lld", (long long)N);
+    if (S < 1 || S > REFIT_KMAX) return fail("n_test must be in [1, %d], got %d", REFIT_KMAX, S);
+    const ProfileIO io{device, counts, N, n_features, signatures, K, test, S, candidates, min_iterations, max_iterations, conv_test_freq, tol, tested,
+                       exposures, errors, timings};
+    std::vector<int> prob_n, prob_s, end, h_nt, h_br;
+    std::vector<double> hhat, f1, h_c, h_f, h_lo, h_hi;
+    std::vector<size_t> prob_pair;
+    ProfileRun r;
+    CK(profile_observed(io, r));
+    const int T = E + J;
+    const size_t NS = (size_t)N * S, NP = r.NP;
+    const double nan = std::nan("");
+    for (double* out : {lower, upper, estimate, statistic, null_errors}) std::fill(out, out + NS, nan);
+    std::fill(bracketed, bracketed + NS, (uint8_t)0);
+    std::fill(n_trials, n_trials + 2 * NS, 0);
+    if (trace_values) std::fill(trace_values, trace_values + 2 * NS * T, nan), std::fill(trace_profile, trace_profile + 2 * NS * T, nan);
+    if (NP == 0) return 0;
+
+    // a problem is a pair and one end; a lower end with g(0) <= delta is 0.0 without a trial
+    for (size_t j = 0; j < NP; ++j) {
+        const size_t o = r.slot[j];
+        const double hh = r.h_H1[j * K + r.pair_s[j]];
+        estimate[o] = hh, statistic[o] = r.h_stat[j], null_errors[o] = r.h_f[2 * j + 1];
+        lower[o] = 0.0;
+        for (int which = 0; which < 2; ++which) {
+            if (which == 0 && r.h_stat[j] <= delta) continue;
+            prob_pair.push_back(j), prob_n.push_back(r.pair_n[j]), prob_s.push_back(r.pair_s[j]), end.push_back(which);
+            hhat.push_back(hh), f1.push_back(r.h_f[2 * j]);
+        }
+    }
+    const size_t P = prob_pair.size();
+    h_c.resize(P * T), h_f.resize(P * T), h_lo.resize(P), h_hi.resize(P), h_nt.resize(P), h_br.resize(P);
+    DevBufs& d = *r.d;
+    ProfileArgs a{};
+    a.prob_n = profile_upload(d, prob_n), a.prob_s = profile_upload(d, prob_s), a.end = profile_upload(d, end);
+    a.hhat = profile_upload(d, hhat), a.f1 = profile_upload(d, f1);
+    a.trial_c = d.get<double>(P * T), a.trial_f = d.get<double>(P * T), a.trial_nit = d.get<int>(P * T), a.trial_conv = d.get<int>(P * T);
+    a.lo = d.get<double>(P), a.hi = d.get<double>(P), a.n_trials = d.get<int>(P), a.bracketed = d.get<int>(P);
+    if (!a.prob_n || !a.prob_s || !a.end || !a.hhat || !a.f1 || !a.trial_c || !a.trial_f || !a.trial_nit || !a.trial_conv || !a.lo || !a.hi ||
+        !a.n_trials || !a.bracketed)
+        return fail("hipMalloc or upload failed (%zu problems of %d trials, %d signatures)", P, T, K);
+    a.P = (int64_t)P, a.T = T, a.n_bisections = J, a.max_expansions = E, a.delta = delta;
+    CK(r.launch(io, a));
+    HIPCK(hipMemcpyAsync(h_c.data(), a.trial_c, h_c.size() * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(h_f.data(), a.trial_f, h_f.size() * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(h_lo.data(), a.lo, P * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(h_hi.data(), a.hi, P * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(h_nt.data(), a.n_trials, P * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipMemcpyAsync(h_br.data(), a.bracketed, P * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    HIPCK(hipStreamSynchronize(d.stream));
+    for (size_t p = 0; p < P; ++p) {
+        const size_t o = r.slot[prob_pair[p]];
+        const int which = end[p];
+        if (which == 0) lower[o] = h_lo[p];
+        else upper[o] = h_br[p] ? h_hi[p] : INFINITY, bracketed[o] = h_br[p] != 0;
+        n_trials[2 * o + which] = h_nt[p];
+        if (trace_values)
+            for (int i = 0; i < h_nt[p]; ++i) {
+                trace_values[(2 * o + which) * T + i] = h_c[p * T + i];
+                trace_profile[(2 * o + which) * T + i] = h_f[p * T + i] - f1[p];  // the kernel's own g, one rounded subtraction
+            }
+    }
+    return r.times(io, (int64_t)P);
 }
