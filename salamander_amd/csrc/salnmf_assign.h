@@ -10,7 +10,7 @@
 // 0.0 and solves; if f' - f <= max_kl_increase (false for a NaN) the trial's h, f and A \ {c} are accepted, otherwise c is
 // protected for good and h, f stay.  The procedure ends when there is no candidate or one signature is left.
 //
-// assign_kernel is refit_kernel with a state machine per lane column.  max_iterations is a multiple of conv_test_freq, so
+// assign_kernel is refit_kernel with a state machine per lane column, on the same solve_* pieces (salnmf_refit.h).  max_iterations is a multiple of conv_test_freq, so
 // every solve ends at a test and the next one starts there: the tests of all 16 columns fall on the same iterations of the
 // wave's loop whatever each column is doing.  At a test where some column's solve ends, those columns take their decision,
 // write their next start into h, and the loop body runs again from the P^T product without stepping: that pass is the new
@@ -73,21 +73,6 @@ struct AssignSelectArgs {
 
 #ifdef SALNMF_REFIT_KERNELS
 
-// U^T of a step from its P^T (the loop below has the same statements in line): the update factors at h
-template <int KT>
-__device__ __forceinline__ void assign_update_factors(const double (&x)[VT][4], const d4 (&pr)[VT], const double* wu, int V, int q, d4 (&u)[KT]) {
-#pragma unroll
-    for (int kt = 0; kt < KT; ++kt) u[kt] = (d4){0, 0, 0, 0};
-#pragma unroll
-    for (int vt = 0; vt < VT; ++vt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const double av = (16 * vt + 4 * r + q < V) ? div_path(x[vt][r], pr[vt][r]) : 0.0;
-#pragma unroll
-            for (int kt = 0; kt < KT; ++kt) u[kt] = mfma(wu[16 * kt * WS + 4 * (4 * vt + r)], av, u[kt]);
-        }
-}
-
 template <int KT, bool EX>
 __global__ void __launch_bounds__(BLOCK) assign_kernel(AssignArgs a) {
     constexpr int KP = 16 * KT;
@@ -97,35 +82,19 @@ __global__ void __launch_bounds__(BLOCK) assign_kernel(AssignArgs a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int c16 = lane & 15, q = lane >> 4;
     const int V = a.V, K = a.K;
-    for (int i = tid; i < KP * WS; i += BLOCK) {
-        const int k = i / WS, v = i - k * WS;
-        Wl[i] = (k < K && v < V) ? a.W[k * V + v] : 0.0;
-    }
-    __syncthreads();
+    solve_stage_w<KT>(Wl, a.W, K, V, tid);
     const int64_t ntiles = (a.P + 15) / 16;
     const double* wp = Wl + q * WS + c16;
     const double* wu = Wl + c16 * WS + q;
 
     for (;;) {
-        unsigned ticket = 0;
-        if (lane == 0) ticket = atomicAdd(a.next_tile, 1u);
-        const int64_t tile = (int64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)ticket);
+        const int64_t tile = solve_take_tile(a.next_tile, lane);
         if (tile >= ntiles) break;
         const int64_t p = tile * 16 + c16;
         const int64_t row = p < a.P ? p : a.P - 1;
-        const double* xs = a.X + row * V;
         double* hrow = a.H + row * K;
         double x[VT][4];
-        double t = 0.0;
-#pragma unroll
-        for (int vt = 0; vt < VT; ++vt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int v = 16 * vt + 4 * r + q;
-                x[vt][r] = v < V ? xs[v] : 0.0;
-                t += x[vt][r];
-            }
-        t = rows_sum(t);
+        const double t = solve_load_row(a.X + row * V, V, q, x);
         // the column's state, the same in its four lanes.  A lane column past the end of the list is finished from the start:
         // it recomputes the last problem's first step and touches no memory.
         unsigned act[NW], prot[NW];
@@ -218,8 +187,7 @@ __global__ void __launch_bounds__(BLOCK) assign_kernel(AssignArgs a) {
                 bool stop = false;
                 int cv = 0;
                 if (mode != 2 && (fresh || !repass)) {
-                    if (itl > 0 && itl >= a.min_it && fabs(prev - cur) / fabs(prev) < a.tol) stop = true, cv = 1;
-                    if (itl == a.max_it) stop = true;
+                    stop = solve_stop(itl, prev, cur, a.min_it, a.max_it, a.tol, cv);
                     prev = cur;
                 }
                 fresh = false;
@@ -231,13 +199,7 @@ __global__ void __launch_bounds__(BLOCK) assign_kernel(AssignArgs a) {
                     const bool owner = q == (cand & 3);
                     if (stop) nsum += itl, conv &= cv;
                     if (dense && a.dH) {
-#pragma unroll
-                        for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) {
-                                const int k = 16 * kt + 4 * r + q;
-                                if (k < K) a.dH[p * K + k] = h[kt][r];
-                            }
+                        solve_store_column<KT>(a.dH + p * K, h, K, q);
                         if (q == 0) a.derr[p] = cur, a.dnit[p] = itl, a.dconv[p] = cv;
                     }
                     if (trial && owner && a.kl) a.kl[p * K + cand] = delta;
@@ -312,7 +274,7 @@ __global__ void __launch_bounds__(BLOCK) assign_kernel(AssignArgs a) {
                     if (__any(select)) {
                         // the next re-addition candidate: largest update factor in the pool, lowest index on ties
                         d4 u[KT];
-                        assign_update_factors<KT>(x, pr, wu, V, q, u);
+                        solve_update_factors<KT>(x, pr, wu, V, q, u);
                         unsigned el[NW];
 #pragma unroll
                         for (int w = 0; w < NW; ++w) el[w] = (~act[w] & ~tried[w]) >> q;
@@ -353,16 +315,7 @@ __global__ void __launch_bounds__(BLOCK) assign_kernel(AssignArgs a) {
             }
             --until_test;
             d4 u[KT];
-#pragma unroll
-            for (int kt = 0; kt < KT; ++kt) u[kt] = (d4){0, 0, 0, 0};
-#pragma unroll
-            for (int vt = 0; vt < VT; ++vt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const double av = (16 * vt + 4 * r + q < V) ? div_path(x[vt][r], pr[vt][r]) : 0.0;
-#pragma unroll
-                    for (int kt = 0; kt < KT; ++kt) u[kt] = mfma(wu[16 * kt * WS + 4 * (4 * vt + r)], av, u[kt]);
-                }
+            solve_update_factors<KT>(x, pr, wu, V, q, u);
 #pragma unroll
             for (int kt = 0; kt < KT; ++kt)
 #pragma unroll

@@ -19,6 +19,8 @@
 // Reduction, one thread per (pair, level) walking a and, inside, b, both ascending: e_a = #{b : t_b >= t*_a} over the pair's B
 // null statistics (false for a NaN on either side); draw a is DETECTED iff t*_a is not NaN and e_a <= max_exceed;
 // n_detected counts them; alt_mean is the sum of t*_a from 0.0 in ascending a, divided by A.
+// The solves of the alternative draws are presence_kernel launches (salnmf_presence.h, on the solve_* pieces of salnmf_refit.h),
+// issued by the same draw-and-solve loop as the presence test's null draws (salnmf_refit.hip: pair_draw_solve).
 #pragma once
 #include <hip/hip_runtime.h>
 

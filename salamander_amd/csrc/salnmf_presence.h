@@ -13,7 +13,7 @@
 // draw's word has these upper 16 bits (the resampler's is 0, the split's 0x53504C54, the goodness-of-fit draw's 0x474F4644) --
 // and the tested signature, so a pair's draws depend on (seed, n, s, b) and on h0, and on nothing else.
 //
-// presence_kernel is refit_kernel's tile loop with assign_kernel's way of letting one solve follow another: max_iterations is a
+// presence_kernel is refit_kernel's tile loop (the solve_* pieces of salnmf_refit.h) with assign_kernel's way of letting one solve follow another: max_iterations is a
 // multiple of conv_test_freq, every solve ends at a test, and the columns whose alternative solve has just ended reset their
 // start and run the loop body again from the P^T product without stepping -- the null solve's iteration-0 test.  x is loaded
 // once for both solves.  Branches are taken on ballots, the transitions are predicated per column, and a column's numbers
@@ -84,47 +84,24 @@ __global__ void __launch_bounds__(BLOCK) presence_kernel(PresenceArgs a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int c16 = lane & 15, q = lane >> 4;
     const int V = a.V, K = a.K;
-    for (int i = tid; i < KP * WS; i += BLOCK) {
-        const int k = i / WS, v = i - k * WS;
-        Wl[i] = (k < K && v < V) ? a.W[k * V + v] : 0.0;
-    }
-    __syncthreads();
+    solve_stage_w<KT>(Wl, a.W, K, V, tid);
     const int64_t ntiles = (a.P + 15) / 16;
     const double* wp = Wl + q * WS + c16;
     const double* wu = Wl + c16 * WS + q;
 
     for (;;) {
-        unsigned ticket = 0;
-        if (lane == 0) ticket = atomicAdd(a.next_tile, 1u);
-        const int64_t tile = (int64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)ticket);
+        const int64_t tile = solve_take_tile(a.next_tile, lane);
         if (tile >= ntiles) break;
         const int64_t p = tile * 16 + c16;
         const int64_t row = p < a.P ? p : a.P - 1;
         const int64_t pair = row % a.NP;
         const int n = a.pair_n[pair], s = a.pair_s[pair];
-        const double* xs = a.X + (a.by_sample ? (int64_t)n : row) * V;
         double x[VT][4];
-        double t = 0.0;
-#pragma unroll
-        for (int vt = 0; vt < VT; ++vt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int v = 16 * vt + 4 * r + q;
-                x[vt][r] = v < V ? xs[v] : 0.0;
-                t += x[vt][r];
-            }
-        t = rows_sum(t);
+        const double t = solve_load_row(a.X + (a.by_sample ? (int64_t)n : row) * V, V, q, x);
         // the column's set, the same in its four lanes: C for the first solve, C \ {s} for the second.  A lane column past the
         // end of the list is finished from the start: it recomputes the last problem's first step and touches no memory.
         unsigned act[NW];
-        int nc = 0;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {
-            const int m = K - 32 * w;
-            act[w] = m >= 32 ? ~0u : m > 0 ? (1u << m) - 1u : 0u;
-            if (a.cand) act[w] &= a.cand[(int64_t)n * NW + w];
-            nc += __popc(act[w]);
-        }
+        const int nc = solve_candidate_words<NW>(K, a.cand, (int64_t)n * NW, act);
         d4 h[KT];
         auto start = [&](int members) {
             const double h0 = t / (double)members;
@@ -139,15 +116,7 @@ __global__ void __launch_bounds__(BLOCK) presence_kernel(PresenceArgs a) {
         int itl = 0;
         double prev = 0.0, f1 = 0.0;
         auto latch = [&](double* H, int which, double cur, int cv) {  // (the caller's predicate holds)
-            if (H) {
-#pragma unroll
-                for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int k = 16 * kt + 4 * r + q;
-                        if (k < K) H[p * K + k] = h[kt][r];
-                    }
-            }
+            if (H) solve_store_column<KT>(H + p * K, h, K, q);
             if (q == 0) {
                 a.nit[2 * p + which] = itl;
                 if (a.f) a.f[2 * p + which] = cur, a.conv[2 * p + which] = cv;
@@ -171,8 +140,7 @@ __global__ void __launch_bounds__(BLOCK) presence_kernel(PresenceArgs a) {
                 bool stop = false;
                 int cv = 0;
                 if (mode != 2 && (fresh || !repass)) {
-                    if (itl > 0 && itl >= a.min_it && fabs(prev - cur) / fabs(prev) < a.tol) stop = true, cv = 1;
-                    if (itl == a.max_it) stop = true;
+                    stop = solve_stop(itl, prev, cur, a.min_it, a.max_it, a.tol, cv);
                     prev = cur;
                 }
                 fresh = false;
@@ -201,7 +169,7 @@ __global__ void __launch_bounds__(BLOCK) presence_kernel(PresenceArgs a) {
             }
             --until_test;
             d4 u[KT];
-            assign_update_factors<KT>(x, pr, wu, V, q, u);
+            solve_update_factors<KT>(x, pr, wu, V, q, u);
 #pragma unroll
             for (int kt = 0; kt < KT; ++kt)
 #pragma unroll

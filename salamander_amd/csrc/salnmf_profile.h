@@ -20,7 +20,8 @@
 //                (bracketed = 0); otherwise J times m = 0.5 (lo + hi), g(m) > delta ? hi = m : lo = m; the end is hi.
 //     A comparison with a NaN is false.  Both ends are the outer ones of their last bracket.
 //
-// profile_kernel is presence_kernel's tile loop and tile tickets with its two-state mode made a per-column trial machine: a
+// profile_kernel is presence_kernel's tile loop and tile tickets (on the solve_* pieces of salnmf_refit.h where they cost
+// it no register) with its two-state mode made a per-column trial machine: a
 // column whose solve ends at a test stores the trial, takes its next value, resets its start and runs the loop body again from
 // the P^T product without stepping -- the next solve's iteration-0 test -- exactly as the null solve follows the alternative
 // there.  The frozen signature is one bit beside act[]; the step keeps an entry that is finished, 0.0 or frozen.  x is loaded
@@ -161,8 +162,7 @@ __global__ void __launch_bounds__(BLOCK) profile_kernel(ProfileArgs a) {
                 bool stop = false;
                 int cv = 0;
                 if (!done && (fresh || !repass)) {
-                    if (itl > 0 && itl >= a.min_it && fabs(prev - cur) / fabs(prev) < a.tol) stop = true, cv = 1;
-                    if (itl == a.max_it) stop = true;
+                    stop = solve_stop(itl, prev, cur, a.min_it, a.max_it, a.tol, cv);
                     prev = cur;
                 }
                 fresh = false;
@@ -171,15 +171,7 @@ __global__ void __launch_bounds__(BLOCK) profile_kernel(ProfileArgs a) {
                         // the trial's results (ti < T: the host's counts in grid mode; in search mode ne <= E, nb <= J at an upper
                         // and nb <= J + E at a lower end, which does not expand)
                         const int64_t o = p * a.T + ti;
-                        if (a.trial_H) {
-#pragma unroll
-                            for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-                                for (int r = 0; r < 4; ++r) {
-                                    const int k = 16 * kt + 4 * r + q;
-                                    if (k < K) a.trial_H[o * K + k] = h[kt][r];
-                                }
-                        }
+                        if (a.trial_H) solve_store_column<KT>(a.trial_H + o * K, h, K, q);
                         if (q == 0) {
                             a.trial_f[o] = cur, a.trial_nit[o] = itl, a.trial_conv[o] = cv;
                             if (search) a.trial_c[o] = c;
@@ -224,7 +216,7 @@ __global__ void __launch_bounds__(BLOCK) profile_kernel(ProfileArgs a) {
             }
             --until_test;
             d4 u[KT];
-            assign_update_factors<KT>(x, pr, wu, V, q, u);
+            solve_update_factors<KT>(x, pr, wu, V, q, u);
 #pragma unroll
             for (int kt = 0; kt < KT; ++kt)
 #pragma unroll

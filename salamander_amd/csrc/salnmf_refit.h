@@ -21,6 +21,12 @@
 // result cannot depend on its neighbours in the tile, on the tile it lands in, or on when the others stop.  A wave leaves its
 // tile when all 16 problems are latched; every branch and trip count is wave-uniform (ballots).  Lane columns beyond the end
 // of the list recompute the last problem and store nothing.
+//
+// What this kernel shares with assign_kernel, presence_kernel and profile_kernel is written once, as the solve_* pieces in
+// front of it: the W fill, the tile ticket, the row load, the update factors, the store of an h column, the candidate words and
+// the stop rule.  A further analysis on this family writes its own loop and state machine around them.
+// A kernel calls a piece only where the call leaves its registers as they were (profiles/refit_pieces/README.md): these
+// kernels fill the register file, and where a piece moved the allocation the kernel keeps the statements in line.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -84,6 +90,99 @@ __device__ __forceinline__ double refit_objective(const double (&x)[VT][4], cons
     return rows_sum(acc);
 }
 
+// ---- the pieces of a tile solve.  refit_kernel below, assign_kernel (salnmf_assign.h), presence_kernel (salnmf_presence.h) and
+// profile_kernel (salnmf_profile.h) are built from them: each kernel keeps its own loop and its own per-column state machine
+// and calls these for what all four do alike.  All are forced inline and hold no state: no LDS but W's, nothing per wave.
+// Kept in line where the call moved a kernel's register allocation: the P^T product in all four (as a piece it cost 21 of the
+// 30 instantiations 2 to 20 AGPRs, so there is none), the stop rule in refit_kernel, and the W fill, ticket, row load and
+// candidate words in profile_kernel.
+
+// W [16 KT][WS] into LDS, zero padded (rows k >= K and columns v >= V are 0), and the barrier after it
+template <int KT>
+__device__ __forceinline__ void solve_stage_w(double* Wl, const double* W, int K, int V, int tid) {
+    for (int i = tid; i < 16 * KT * WS; i += BLOCK) {
+        const int k = i / WS, v = i - k * WS;
+        Wl[i] = (k < K && v < V) ? W[k * V + v] : 0.0;
+    }
+    __syncthreads();
+}
+
+// The wave's next tile off the list's head (uniform)
+__device__ __forceinline__ int64_t solve_take_tile(unsigned* next_tile, int lane) {
+    unsigned ticket = 0;
+    if (lane == 0) ticket = atomicAdd(next_tile, 1u);
+    return (int64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)ticket);
+}
+
+// The lane's 24 entries of its column's row (rows v = 16 vt + 4 r + q, 0 beyond V) -> the row's sum, alike in the column's lanes
+__device__ __forceinline__ double solve_load_row(const double* xs, int V, int q, double (&x)[VT][4]) {
+    double t = 0.0;
+#pragma unroll
+    for (int vt = 0; vt < VT; ++vt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int v = 16 * vt + 4 * r + q;
+            x[vt][r] = v < V ? xs[v] : 0.0;
+            t += x[vt][r];
+        }
+    return rows_sum(t);
+}
+
+// U^T of a step from its P^T, the update factors at h: wu = Wl + c16 WS + q, A[i = k][v] = W[16 kt + c16][4 s + q]
+template <int KT>
+__device__ __forceinline__ void solve_update_factors(const double (&x)[VT][4], const d4 (&pr)[VT], const double* wu, int V, int q, d4 (&u)[KT]) {
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt) u[kt] = (d4){0, 0, 0, 0};
+#pragma unroll
+    for (int vt = 0; vt < VT; ++vt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const double av = (16 * vt + 4 * r + q < V) ? div_path(x[vt][r], pr[vt][r]) : 0.0;
+#pragma unroll
+            for (int kt = 0; kt < KT; ++kt) u[kt] = mfma(wu[16 * kt * WS + 4 * (4 * vt + r)], av, u[kt]);
+        }
+}
+
+// The lane's entries of h into row `dst` of a [P][K] array
+template <int KT>
+__device__ __forceinline__ void solve_store_column(double* dst, const d4 (&h)[KT], int K, int q) {
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int k = 16 * kt + 4 * r + q;
+            if (k < K) dst[k] = h[kt][r];
+        }
+}
+
+// A column's candidate set as NW words: all K signatures, or words row .. row + NW - 1 of `cand` -> the members' count
+template <int NW>
+__device__ __forceinline__ int solve_candidate_words(int K, const unsigned* cand, int64_t row, unsigned (&act)[NW]) {
+    int nc = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+        const int m = K - 32 * w;
+        act[w] = m >= 32 ? ~0u : m > 0 ? (1u << m) - 1u : 0u;
+        if (cand) act[w] &= cand[row + w];
+        nc += __popc(act[w]);
+    }
+    return nc;
+}
+
+// The tolerance test of a solve at its iteration itl (a NaN comparison is false)
+__device__ __forceinline__ bool solve_converged(int itl, double prev, double cur, int min_it, double tol) {
+    return itl > 0 && itl >= min_it && fabs(prev - cur) / fabs(prev) < tol;
+}
+
+// The stop rule of a solve whose tests fall on its own iteration count (max_it is a multiple of the test frequency): on the
+// tolerance (cv = 1), else at max_it
+__device__ __forceinline__ bool solve_stop(int itl, double prev, double cur, int min_it, int max_it, double tol, int& cv) {
+    bool stop = false;
+    if (solve_converged(itl, prev, cur, min_it, tol)) stop = true, cv = 1;
+    if (itl == max_it) stop = true;
+    return stop;
+}
+
 template <int KT>
 __global__ void __launch_bounds__(BLOCK) refit_kernel(RefitArgs a) {
     constexpr int KP = 16 * KT;
@@ -91,34 +190,18 @@ __global__ void __launch_bounds__(BLOCK) refit_kernel(RefitArgs a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int c16 = lane & 15, q = lane >> 4;
     const int V = a.V, K = a.K;
-    for (int i = tid; i < KP * WS; i += BLOCK) {
-        const int k = i / WS, v = i - k * WS;
-        Wl[i] = (k < K && v < V) ? a.W[k * V + v] : 0.0;
-    }
-    __syncthreads();
+    solve_stage_w<KT>(Wl, a.W, K, V, tid);
     const int64_t ntiles = (a.P + 15) / 16;
     const double* wp = Wl + q * WS + c16;  // P^T: A[i = v][k] = W[4 s + q][16 vt + c16]
     const double* wu = Wl + c16 * WS + q;  // U^T: A[i = k][v] = W[16 kt + c16][4 s + q]
 
     for (;;) {
-        unsigned ticket = 0;
-        if (lane == 0) ticket = atomicAdd(a.next_tile, 1u);
-        const int64_t tile = (int64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)ticket);
+        const int64_t tile = solve_take_tile(a.next_tile, lane);
         if (tile >= ntiles) break;
         const int64_t p = tile * 16 + c16;
         const int64_t row = p < a.P ? p : a.P - 1;
-        const double* xs = a.X + row * V;
         double x[VT][4];
-        double t = 0.0;
-#pragma unroll
-        for (int vt = 0; vt < VT; ++vt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int v = 16 * vt + 4 * r + q;
-                x[vt][r] = v < V ? xs[v] : 0.0;
-                t += x[vt][r];
-            }
-        t = rows_sum(t);
+        const double t = solve_load_row(a.X + row * V, V, q, x);
         d4 h[KT];
 #pragma unroll
         for (int kt = 0; kt < KT; ++kt)
@@ -152,16 +235,7 @@ __global__ void __launch_bounds__(BLOCK) refit_kernel(RefitArgs a) {
                 if (__all(latched)) break;
             }
             d4 u[KT];
-#pragma unroll
-            for (int kt = 0; kt < KT; ++kt) u[kt] = (d4){0, 0, 0, 0};
-#pragma unroll
-            for (int vt = 0; vt < VT; ++vt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const double av = (16 * vt + 4 * r + q < V) ? div_path(x[vt][r], pr[vt][r]) : 0.0;
-#pragma unroll
-                    for (int kt = 0; kt < KT; ++kt) u[kt] = mfma(wu[16 * kt * WS + 4 * (4 * vt + r)], av, u[kt]);
-                }
+            solve_update_factors<KT>(x, pr, wu, V, q, u);
 #pragma unroll
             for (int kt = 0; kt < KT; ++kt)
 #pragma unroll
@@ -171,13 +245,7 @@ __global__ void __launch_bounds__(BLOCK) refit_kernel(RefitArgs a) {
                 }
         }
         if (p < a.P) {
-#pragma unroll
-            for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int k = 16 * kt + 4 * r + q;
-                    if (k < K) a.H[p * K + k] = h[kt][r];
-                }
+            solve_store_column<KT>(a.H + p * K, h, K, q);
             if (q == 0) {
                 a.err[p] = err;
                 a.nit[p] = nit;

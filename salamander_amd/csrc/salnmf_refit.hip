@@ -7,6 +7,8 @@
 // and of that test's power analysis (salnmf_signature_power; salnmf_power.h: its three kernels in salnmf_batch.hip), DESIGN.md section 18;
 // and of the profile likelihood of one exposure and its interval (salnmf_profile_likelihood, salnmf_exposure_intervals;
 // salnmf_profile.h: profile_kernel), DESIGN.md section 19.
+// The four tile-solve kernels share the solve_* pieces of salnmf_refit.h; the drivers below share one kit:
+// launch_tiles, Spans, chunk_rows, fill_reduce, upload / download, and for the pair calls pair_observed and pair_draw_solve.
 #define SALNMF_TEMPLATES_ONLY 1
 #define SALNMF_REFIT_KERNELS 1
 #include "../../include/salnmf.h"
@@ -21,7 +23,9 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <memory>
+#include <type_traits>
 #include <vector>
 
 using namespace salnmf;
@@ -114,81 +118,126 @@ int refit_prepare(int device, const double* counts, int64_t N, int V, const doub
     return 0;
 }
 
-int launch_refit(const RefitArgs& a, int cus, hipStream_t stream) {
-    const int64_t ntiles = (a.P + 15) / 16;
-    // one workgroup per CU (the kernel's registers leave room for one wave per SIMD); waves fetch tiles until the list is empty
+// ---- the host kit of the family: one tile launcher, one span timer, one chunk rule, one reduce fill.
+
+// What every tile-solve kernel's launch does: one workgroup per CU (the kernels' registers leave room for one wave per SIMD; waves
+// fetch tiles until the list is empty), the list's head reset, and the instantiation for (K + 15) / 16 signature tiles, which
+// `launch` gets as a std::integral_constant.
+template <typename Launch>
+int launch_tiles(const char* what, int64_t P, int K, unsigned* next_tile, int cus, hipStream_t stream, Launch&& launch) {
+    const int64_t ntiles = (P + 15) / 16;
     const dim3 grid((unsigned)std::min<int64_t>((int64_t)cus, (ntiles + WAVES - 1) / WAVES));
-    HIPCK(hipMemsetAsync(a.next_tile, 0, sizeof(unsigned), stream));
-    switch ((a.K + 15) / 16) {
-        case 1: hipLaunchKernelGGL(refit_kernel<1>, grid, dim3(BLOCK), 0, stream, a); break;
-        case 2: hipLaunchKernelGGL(refit_kernel<2>, grid, dim3(BLOCK), 0, stream, a); break;
-        case 3: hipLaunchKernelGGL(refit_kernel<3>, grid, dim3(BLOCK), 0, stream, a); break;
-        case 4: hipLaunchKernelGGL(refit_kernel<4>, grid, dim3(BLOCK), 0, stream, a); break;
-        case 5: hipLaunchKernelGGL(refit_kernel<5>, grid, dim3(BLOCK), 0, stream, a); break;
-        case 6: hipLaunchKernelGGL(refit_kernel<6>, grid, dim3(BLOCK), 0, stream, a); break;
-        default: return fail("no refit kernel for %d signatures", a.K);
+    HIPCK(hipMemsetAsync(next_tile, 0, sizeof(unsigned), stream));
+    switch ((K + 15) / 16) {
+        case 1: launch(std::integral_constant<int, 1>{}, grid); break;
+        case 2: launch(std::integral_constant<int, 2>{}, grid); break;
+        case 3: launch(std::integral_constant<int, 3>{}, grid); break;
+        case 4: launch(std::integral_constant<int, 4>{}, grid); break;
+        case 5: launch(std::integral_constant<int, 5>{}, grid); break;
+        case 6: launch(std::integral_constant<int, 6>{}, grid); break;
+        default: return fail("no %s kernel for %d signatures", what, K);
     }
     HIPCK(hipGetLastError());
     return 0;
+}
+
+int launch_refit(const RefitArgs& a, int cus, hipStream_t stream) {
+    return launch_tiles("refit", a.P, a.K, a.next_tile, cus, stream,
+                        [&](auto kt, dim3 grid) { hipLaunchKernelGGL(refit_kernel<decltype(kt)::value>, grid, dim3(BLOCK), 0, stream, a); });
 }
 
 int launch_assign(const AssignArgs& a, int cus, hipStream_t stream) {
-    const int64_t ntiles = (a.P + 15) / 16;
-    const dim3 grid((unsigned)std::min<int64_t>((int64_t)cus, (ntiles + WAVES - 1) / WAVES));  // as launch_refit
-    HIPCK(hipMemsetAsync(a.next_tile, 0, sizeof(unsigned), stream));
     // candidate sets, required signatures and the re-addition pass have instantiations of their own
-    const int kt = (a.K + 15) / 16 + (a.cand || a.req || a.readd ? 8 : 0);
-    switch (kt) {
-        case 1: hipLaunchKernelGGL((assign_kernel<1, false>), grid, dim3(BLOCK), 0, stream, a); break;
-        case 2: hipLaunchKernelGGL((assign_kernel<2, false>), grid, dim3(BLOCK), 0, stream, a); break;
-        case 3: hipLaunchKernelGGL((assign_kernel<3, false>), grid, dim3(BLOCK), 0, stream, a); break;
-        case 4: hipLaunchKernelGGL((assign_kernel<4, false>), grid, dim3(BLOCK), 0, stream, a); break;
-        case 5: hipLaunchKernelGGL((assign_kernel<5, false>), grid, dim3(BLOCK), 0, stream, a); break;
-        case 6: hipLaunchKernelGGL((assign_kernel<6, false>), grid, dim3(BLOCK), 0, stream, a); break;
-        case 9: hipLaunchKernelGGL((assign_kernel<1, true>), grid, dim3(BLOCK), 0, stream, a); break;
-        case 10: hipLaunchKernelGGL((assign_kernel<2, true>), grid, dim3(BLOCK), 0, stream, a); break;
-        case 11: hipLaunchKernelGGL((assign_kernel<3, true>), grid, dim3(BLOCK), 0, stream, a); break;
-        case 12: hipLaunchKernelGGL((assign_kernel<4, true>), grid, dim3(BLOCK), 0, stream, a); break;
-        case 13: hipLaunchKernelGGL((assign_kernel<5, true>), grid, dim3(BLOCK), 0, stream, a); break;
-        case 14: hipLaunchKernelGGL((assign_kernel<6, true>), grid, dim3(BLOCK), 0, stream, a); break;
-        default: return fail("no assignment kernel for %d signatures", a.K);
-    }
-    HIPCK(hipGetLastError());
-    return 0;
+    const bool ex = a.cand || a.req || a.readd;
+    return launch_tiles("assignment", a.P, a.K, a.next_tile, cus, stream, [&](auto kt, dim3 grid) {
+        if (ex) hipLaunchKernelGGL((assign_kernel<decltype(kt)::value, true>), grid, dim3(BLOCK), 0, stream, a);
+        else hipLaunchKernelGGL((assign_kernel<decltype(kt)::value, false>), grid, dim3(BLOCK), 0, stream, a);
+    });
 }
 
 int launch_presence(const PresenceArgs& a, int cus, hipStream_t stream) {
-    const int64_t ntiles = (a.P + 15) / 16;
-    const dim3 grid((unsigned)std::min<int64_t>((int64_t)cus, (ntiles + WAVES - 1) / WAVES));  // as launch_refit
-    HIPCK(hipMemsetAsync(a.next_tile, 0, sizeof(unsigned), stream));
-    switch ((a.K + 15) / 16) {
-        case 1: hipLaunchKernelGGL(presence_kernel<1>, grid, dim3(BLOCK), 0, stream, a); break;
-        case 2: hipLaunchKernelGGL(presence_kernel<2>, grid, dim3(BLOCK), 0, stream, a); break;
-        case 3: hipLaunchKernelGGL(presence_kernel<3>, grid, dim3(BLOCK), 0, stream, a); break;
-        case 4: hipLaunchKernelGGL(presence_kernel<4>, grid, dim3(BLOCK), 0, stream, a); break;
-        case 5: hipLaunchKernelGGL(presence_kernel<5>, grid, dim3(BLOCK), 0, stream, a); break;
-        case 6: hipLaunchKernelGGL(presence_kernel<6>, grid, dim3(BLOCK), 0, stream, a); break;
-        default: return fail("no presence kernel for %d signatures", a.K);
-    }
-    HIPCK(hipGetLastError());
-    return 0;
+    return launch_tiles("presence", a.P, a.K, a.next_tile, cus, stream,
+                        [&](auto kt, dim3 grid) { hipLaunchKernelGGL(presence_kernel<decltype(kt)::value>, grid, dim3(BLOCK), 0, stream, a); });
 }
 
 int launch_profile(const ProfileArgs& a, int cus, hipStream_t stream) {
-    const int64_t ntiles = (a.P + 15) / 16;
-    const dim3 grid((unsigned)std::min<int64_t>((int64_t)cus, (ntiles + WAVES - 1) / WAVES));  // as launch_refit
-    HIPCK(hipMemsetAsync(a.next_tile, 0, sizeof(unsigned), stream));
-    switch ((a.K + 15) / 16) {
-        case 1: hipLaunchKernelGGL(profile_kernel<1>, grid, dim3(BLOCK), 0, stream, a); break;
-        case 2: hipLaunchKernelGGL(profile_kernel<2>, grid, dim3(BLOCK), 0, stream, a); break;
-        case 3: hipLaunchKernelGGL(profile_kernel<3>, grid, dim3(BLOCK), 0, stream, a); break;
-        case 4: hipLaunchKernelGGL(profile_kernel<4>, grid, dim3(BLOCK), 0, stream, a); break;
-        case 5: hipLaunchKernelGGL(profile_kernel<5>, grid, dim3(BLOCK), 0, stream, a); break;
-        case 6: hipLaunchKernelGGL(profile_kernel<6>, grid, dim3(BLOCK), 0, stream, a); break;
-        default: return fail("no profile kernel for %d signatures", a.K);
+    return launch_tiles("profile", a.P, a.K, a.next_tile, cus, stream,
+                        [&](auto kt, dim3 grid) { hipLaunchKernelGGL(profile_kernel<decltype(kt)::value>, grid, dim3(BLOCK), 0, stream, a); });
+}
+
+// Device-event spans around groups of launches on d's stream, summed per group; nothing is recorded unless `on`.
+struct Spans {
+    static constexpr int GROUPS = 7;  // the most any driver has (the power analysis)
+    DevBufs* d = nullptr;
+    bool on = false;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> spans[GROUPS];
+
+    void start(DevBufs& bufs, bool timing) { d = &bufs, on = timing; }
+    template <typename F>
+    int timed(int which, F&& body) {
+        if (which < 0 || which >= GROUPS) return fail("span group %d out of range", which);
+        hipEvent_t e0 = on ? d->mark() : nullptr;
+        CK(body());
+        hipEvent_t e1 = on ? d->mark() : nullptr;
+        if (on && (!e0 || !e1)) return fail("event record failed");
+        if (on) spans[which].emplace_back(e0, e1);
+        return 0;
     }
-    HIPCK(hipGetLastError());
+    // (after the stream has been waited for)
+    int total_ms(int which, double* out) {
+        double total = 0.0;
+        for (const auto& pr : spans[which]) {
+            float ms = 0.f;
+            HIPCK(hipEventElapsedTime(&ms, pr.first, pr.second));
+            total += (double)ms;
+        }
+        *out = total;
+        return 0;
+    }
+    // groups 0 .. count - 1 into out[0 .. count - 1]; nothing when timing is off
+    int totals(int count, double* out) {
+        for (int i = 0; on && i < count; ++i) CK(total_ms(i, out + i));
+        return 0;
+    }
+};
+
+// Rows of a chunk buffer: as many of `rows` as budget_bytes allows (0 or less: 256 MiB), at least one
+int64_t chunk_rows(int64_t budget_bytes, size_t row_bytes, int64_t rows) {
+    const int64_t budget = budget_bytes > 0 ? budget_bytes : (int64_t)256 << 20;
+    return std::max<int64_t>(1, std::min<int64_t>(rows, budget / (int64_t)row_bytes));
+}
+
+// The resamples' reduction over H [R][N][K] (red.index is refit_prepare's)
+void fill_reduce(RefitReduceArgs& red, const double* H, double* quant, double* mean, int64_t N, int K, int R, int Q) {
+    red.H = H, red.quant = quant, red.mean = mean;
+    red.N = N, red.K = K, red.R = R, red.Q = Q;
+    red.R2 = 1;
+    while (red.R2 < R) red.R2 <<= 1;
+}
+
+// n entries of `host` in a new buffer of d, copied on its stream: the device pointer, or null (the allocation or the copy
+// failed).  The host side lives until d's destructor has waited for the stream: it is declared before d.
+template <typename T>
+T* upload(DevBufs& d, const T* host, size_t n) {
+    T* dev = d.get<T>(n);
+    if (dev && hipMemcpyAsync(dev, host, n * sizeof(T), hipMemcpyHostToDevice, d.stream) != hipSuccess) return nullptr;
+    return dev;
+}
+template <typename T>
+T* upload(DevBufs& d, const std::vector<T>& host) {
+    return upload(d, host.data(), host.size());
+}
+
+// n entries of the device buffer `src` to `dst` on d's stream (not waited for)
+template <typename D, typename S>
+int download(DevBufs& d, D* dst, const S* src, size_t n) {
+    static_assert(sizeof(D) == sizeof(S), "download: element sizes differ");
+    HIPCK(hipMemcpyAsync(dst, src, n * sizeof(S), hipMemcpyDeviceToHost, d.stream));
     return 0;
+}
+template <typename T, typename S>
+int download(DevBufs& d, std::vector<T>& dst, const S* src) {
+    return download(d, dst.data(), src, dst.size());
 }
 
 }  // namespace
@@ -210,15 +259,14 @@ extern "C" int salnmf_refit_exposures(int device, const double* counts, int64_t 
     const int cus = in.cus;
 
     // resamples per chunk: the [chunk][N][V] buffer stays within chunk_bytes (at least one resample)
-    const int64_t budget = chunk_bytes > 0 ? chunk_bytes : (int64_t)256 << 20;
-    const int chunk = R > 0 ? (int)std::max<int64_t>(1, std::min<int64_t>(R, budget / (int64_t)(sizeof(double) * (size_t)N * V))) : 0;
+    const int chunk = R > 0 ? (int)chunk_rows(chunk_bytes, sizeof(double) * (size_t)N * V, R) : 0;
 
     // (host buffers of the asynchronous copies live until d's destructor has waited for the stream)
     DevBufs d;
     CK(d.own_stream());
     const size_t NR = (size_t)N * (size_t)std::max(R, 1);
-    double* dW = d.get<double>((size_t)K * V);
-    double* dX = d.get<double>((size_t)N * V);
+    double* dW = upload(d, signatures, (size_t)K * V);
+    double* dX = upload(d, x);
     double* dH = d.get<double>((size_t)N * K);
     double* derr = d.get<double>((size_t)N);
     int* dnit = d.get<int>((size_t)N);
@@ -229,7 +277,7 @@ extern "C" int salnmf_refit_exposures(int device, const double* counts, int64_t 
     double *dXr = nullptr, *dHr = nullptr, *derr_r = nullptr, *dquant = nullptr, *dmean = nullptr;
     int *dnit_r = nullptr, *dconv_r = nullptr;
     if (R > 0) {
-        dcounts = d.get<uint32_t>(icounts.size());
+        dcounts = upload(d, icounts);
         dXr = d.get<double>((size_t)chunk * N * V);
         dHr = d.get<double>(NR * K);
         derr_r = d.get<double>(NR);
@@ -239,26 +287,16 @@ extern "C" int salnmf_refit_exposures(int device, const double* counts, int64_t 
         dmean = d.get<double>((size_t)N * K);
         if (!dcounts || !dXr || !dHr || !derr_r || !dnit_r || !dconv_r || !dquant || !dmean)
             return fail("hipMalloc failed (%d resamples of %lld x %d, %d signatures)", R, (long long)N, V, K);
-        HIPCK(hipMemcpyAsync(dcounts, icounts.data(), icounts.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
     }
-    HIPCK(hipMemcpyAsync(dW, signatures, (size_t)K * V * sizeof(double), hipMemcpyHostToDevice, d.stream));
-    HIPCK(hipMemcpyAsync(dX, x.data(), x.size() * sizeof(double), hipMemcpyHostToDevice, d.stream));
 
     RefitArgs a{dX, dW, dH, derr, dnit, dconv, dnext, N, V, K, min_iterations, max_iterations, conv_test_freq, tol};
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> t_refit, t_resample, t_reduce;
-    auto timed = [&](std::vector<std::pair<hipEvent_t, hipEvent_t>>& into, auto&& body) -> int {
-        hipEvent_t e0 = timings ? d.mark() : nullptr;
-        CK(body());
-        hipEvent_t e1 = timings ? d.mark() : nullptr;
-        if (timings && (!e0 || !e1)) return fail("event record failed");
-        if (timings) into.emplace_back(e0, e1);
-        return 0;
-    };
-    CK(timed(t_refit, [&] { return launch_refit(a, cus, d.stream); }));
+    Spans sp;  // resample, refit, reduce
+    sp.start(d, timings != nullptr);
+    CK(sp.timed(1, [&] { return launch_refit(a, cus, d.stream); }));
     int n_chunks = 0;
     for (int first = 0; first < R; first += chunk, ++n_chunks) {
         const int count = std::min(chunk, R - first);
-        CK(timed(t_resample, [&]() -> int {
+        CK(sp.timed(0, [&]() -> int {
             refit_launch_resample(dcounts, dXr, N, V, seed, first, count, d.stream);
             HIPCK(hipGetLastError());
             return 0;
@@ -270,47 +308,28 @@ extern "C" int salnmf_refit_exposures(int device, const double* counts, int64_t 
         c.err = derr_r + (size_t)first * N;
         c.nit = dnit_r + (size_t)first * N;
         c.conv = dconv_r + (size_t)first * N;
-        CK(timed(t_refit, [&] { return launch_refit(c, cus, d.stream); }));
+        CK(sp.timed(1, [&] { return launch_refit(c, cus, d.stream); }));
     }
     if (R > 0) {
-        red.H = dHr;
-        red.quant = dquant;
-        red.mean = dmean;
-        red.N = N;
-        red.K = K;
-        red.R = R;
-        red.Q = Q;
-        red.R2 = 1;
-        while (red.R2 < R) red.R2 <<= 1;
-        CK(timed(t_reduce, [&]() -> int {
+        fill_reduce(red, dHr, dquant, dmean, N, K, R, Q);
+        CK(sp.timed(2, [&]() -> int {
             hipLaunchKernelGGL(refit_reduce_kernel, dim3((unsigned)N), dim3(REFIT_SORT_BLOCK), 0, d.stream, red);
             HIPCK(hipGetLastError());
             return 0;
         }));
-        if (Q > 0) HIPCK(hipMemcpyAsync(exposures_quantiles, dquant, (size_t)Q * N * K * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-        HIPCK(hipMemcpyAsync(exposures_mean, dmean, (size_t)N * K * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-        HIPCK(hipMemcpyAsync(n_iterations_resampled, dnit_r, NR * sizeof(int), hipMemcpyDeviceToHost, d.stream));
-        HIPCK(hipMemcpyAsync(errors_resampled, derr_r, NR * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-        if (exposures_resampled) HIPCK(hipMemcpyAsync(exposures_resampled, dHr, NR * K * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+        if (Q > 0) CK(download(d, exposures_quantiles, dquant, (size_t)Q * N * K));
+        CK(download(d, exposures_mean, dmean, (size_t)N * K));
+        CK(download(d, n_iterations_resampled, dnit_r, NR));
+        CK(download(d, errors_resampled, derr_r, NR));
+        if (exposures_resampled) CK(download(d, exposures_resampled, dHr, NR * K));
     }
-    HIPCK(hipMemcpyAsync(exposures, dH, (size_t)N * K * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(errors, derr, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(n_iterations, dnit, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(converged, dconv, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    CK(download(d, exposures, dH, (size_t)N * K));
+    CK(download(d, errors, derr, (size_t)N));
+    CK(download(d, n_iterations, dnit, (size_t)N));
+    CK(download(d, converged, dconv, (size_t)N));
     HIPCK(hipStreamSynchronize(d.stream));
-    if (timings) {
-        const std::vector<std::pair<hipEvent_t, hipEvent_t>>* sets[3] = {&t_resample, &t_refit, &t_reduce};
-        for (int i = 0; i < 3; ++i) {
-            double total = 0.0;
-            for (const auto& pr : *sets[i]) {
-                float ms = 0.f;
-                HIPCK(hipEventElapsedTime(&ms, pr.first, pr.second));
-                total += (double)ms;
-            }
-            timings[i] = total;
-        }
-        timings[3] = (double)n_chunks;
-    }
+    CK(sp.totals(3, timings));
+    if (timings) timings[3] = (double)n_chunks;
     return 0;
 }
 
@@ -350,14 +369,13 @@ extern "C" int salnmf_assign_signatures_ex(int device, const double* counts, int
     CK(refit_prepare(device, counts, N, V, signatures, K, R, Q, quantiles, min_iterations, max_iterations, conv_test_freq, tol,
                      selection_frequency && exposures_mean && (Q <= 0 || (quantiles && exposures_quantiles)), in, AssignSets{candidates, required, readd}));
     const int cus = in.cus;
-    const int64_t budget = chunk_bytes > 0 ? chunk_bytes : (int64_t)256 << 20;
-    const int chunk = R > 0 ? (int)std::max<int64_t>(1, std::min<int64_t>(R, budget / (int64_t)(sizeof(double) * (size_t)N * V))) : 0;
+    const int chunk = R > 0 ? (int)chunk_rows(chunk_bytes, sizeof(double) * (size_t)N * V, R) : 0;
 
     DevBufs d;
     CK(d.own_stream());
     const size_t NK = (size_t)N * K, NR = (size_t)N * (size_t)std::max(R, 1);
-    double* dW = d.get<double>((size_t)K * V);
-    double* dX = d.get<double>((size_t)N * V);
+    double* dW = upload(d, signatures, (size_t)K * V);
+    double* dX = upload(d, in.x);
     double* dH = d.get<double>(NK);
     double* dHd = d.get<double>(NK);
     double* dkl = d.get<double>(NK);
@@ -376,18 +394,16 @@ extern "C" int salnmf_assign_signatures_ex(int device, const double* counts, int
     uint32_t *dcand = nullptr, *dreq = nullptr;
     int* drround = nullptr;
     double* dkld = nullptr;
-    if (candidates) dcand = d.get<uint32_t>(in.cand.size());
-    if (required) dreq = d.get<uint32_t>(in.req.size());
+    if (candidates) dcand = upload(d, in.cand);
+    if (required) dreq = upload(d, in.req);
     if (readd) drround = d.get<int>(NK), dkld = d.get<double>(NK);
     if ((candidates && !dcand) || (required && !dreq) || (readd && (!drround || !dkld))) return fail("hipMalloc failed (sets of %lld samples)", (long long)N);
-    if (dcand) HIPCK(hipMemcpyAsync(dcand, in.cand.data(), in.cand.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
-    if (dreq) HIPCK(hipMemcpyAsync(dreq, in.req.data(), in.req.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
     uint32_t* dcounts = nullptr;
     double *dXr = nullptr, *dHr = nullptr, *derr_r = nullptr, *dquant = nullptr, *dmean = nullptr, *dfreq = nullptr;
     long long* dnit_r = nullptr;
     int *dconv_r = nullptr, *dntr_r = nullptr;
     if (R > 0) {
-        dcounts = d.get<uint32_t>(in.icounts.size());
+        dcounts = upload(d, in.icounts);
         dXr = d.get<double>((size_t)chunk * N * V);
         dHr = d.get<double>(NR * K);
         derr_r = d.get<double>(NR);
@@ -399,27 +415,17 @@ extern "C" int salnmf_assign_signatures_ex(int device, const double* counts, int
         dfreq = d.get<double>(NK);
         if (!dcounts || !dXr || !dHr || !derr_r || !dnit_r || !dconv_r || !dntr_r || !dquant || !dmean || !dfreq)
             return fail("hipMalloc failed (%d resamples of %lld x %d, %d signatures)", R, (long long)N, V, K);
-        HIPCK(hipMemcpyAsync(dcounts, in.icounts.data(), in.icounts.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
     }
-    HIPCK(hipMemcpyAsync(dW, signatures, (size_t)K * V * sizeof(double), hipMemcpyHostToDevice, d.stream));
-    HIPCK(hipMemcpyAsync(dX, in.x.data(), in.x.size() * sizeof(double), hipMemcpyHostToDevice, d.stream));
 
     AssignArgs a{dX, dW, dH, derr, dnit, dconv, dntr, dact, dround, dkl, dHd, derr_d, dnit_d, dconv_d, dnext, N, V, K,
                  min_iterations, max_iterations, conv_test_freq, tol, max_kl_increase, dcand, dreq, drround, dkld, N, readd};
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> spans[3];  // resample, assign, reduce
-    auto timed = [&](int which, auto&& body) -> int {
-        hipEvent_t e0 = timings ? d.mark() : nullptr;
-        CK(body());
-        hipEvent_t e1 = timings ? d.mark() : nullptr;
-        if (timings && (!e0 || !e1)) return fail("event record failed");
-        if (timings) spans[which].emplace_back(e0, e1);
-        return 0;
-    };
-    CK(timed(1, [&] { return launch_assign(a, cus, d.stream); }));
+    Spans sp;  // resample, assign, reduce
+    sp.start(d, timings != nullptr);
+    CK(sp.timed(1, [&] { return launch_assign(a, cus, d.stream); }));
     int n_chunks = 0;
     for (int first = 0; first < R; first += chunk, ++n_chunks) {
         const int count = std::min(chunk, R - first);
-        CK(timed(0, [&]() -> int {
+        CK(sp.timed(0, [&]() -> int {
             refit_launch_resample(dcounts, dXr, N, V, seed, first, count, d.stream);
             HIPCK(hipGetLastError());
             return 0;
@@ -435,61 +441,43 @@ extern "C" int salnmf_assign_signatures_ex(int device, const double* counts, int
         c.ntrials = dntr_r + (size_t)first * N;
         c.active = nullptr, c.round = nullptr, c.kl = nullptr, c.rround = nullptr, c.kld = nullptr;
         c.dH = nullptr, c.derr = nullptr, c.dnit = nullptr, c.dconv = nullptr;
-        CK(timed(1, [&] { return launch_assign(c, cus, d.stream); }));
+        CK(sp.timed(1, [&] { return launch_assign(c, cus, d.stream); }));
     }
     if (R > 0) {
         RefitReduceArgs& red = in.red;
-        red.H = dHr;
-        red.quant = dquant;
-        red.mean = dmean;
-        red.N = N;
-        red.K = K;
-        red.R = R;
-        red.Q = Q;
-        red.R2 = 1;
-        while (red.R2 < R) red.R2 <<= 1;
+        fill_reduce(red, dHr, dquant, dmean, N, K, R, Q);
         const AssignSelectArgs sel{dHr, dfreq, (int64_t)NK, R};
-        CK(timed(2, [&]() -> int {
+        CK(sp.timed(2, [&]() -> int {
             hipLaunchKernelGGL(refit_reduce_kernel, dim3((unsigned)N), dim3(REFIT_SORT_BLOCK), 0, d.stream, red);
             HIPCK(hipGetLastError());
             hipLaunchKernelGGL(assign_selection_kernel, dim3((unsigned)((NK + 255) / 256)), dim3(256), 0, d.stream, sel);
             HIPCK(hipGetLastError());
             return 0;
         }));
-        if (Q > 0) HIPCK(hipMemcpyAsync(exposures_quantiles, dquant, (size_t)Q * NK * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-        HIPCK(hipMemcpyAsync(exposures_mean, dmean, NK * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-        HIPCK(hipMemcpyAsync(selection_frequency, dfreq, NK * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-        if (exposures_resampled) HIPCK(hipMemcpyAsync(exposures_resampled, dHr, NR * K * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+        if (Q > 0) CK(download(d, exposures_quantiles, dquant, (size_t)Q * NK));
+        CK(download(d, exposures_mean, dmean, NK));
+        CK(download(d, selection_frequency, dfreq, NK));
+        if (exposures_resampled) CK(download(d, exposures_resampled, dHr, NR * K));
     }
-    HIPCK(hipMemcpyAsync(exposures, dH, NK * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(active, dact, NK * sizeof(int), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(removal_round, dround, NK * sizeof(int), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(kl_increase, dkl, NK * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    CK(download(d, exposures, dH, NK));
+    CK(download(d, active, dact, NK));
+    CK(download(d, removal_round, dround, NK));
+    CK(download(d, kl_increase, dkl, NK));
     if (readd) {
-        HIPCK(hipMemcpyAsync(readd_round, drround, NK * sizeof(int), hipMemcpyDeviceToHost, d.stream));
-        HIPCK(hipMemcpyAsync(kl_decrease, dkld, NK * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+        CK(download(d, readd_round, drround, NK));
+        CK(download(d, kl_decrease, dkld, NK));
     }
-    HIPCK(hipMemcpyAsync(errors, derr, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(n_trials, dntr, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(n_iterations, dnit, (size_t)N * sizeof(int64_t), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(converged, dconv, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(dense_exposures, dHd, NK * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(dense_errors, derr_d, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(dense_n_iterations, dnit_d, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(dense_converged, dconv_d, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    CK(download(d, errors, derr, (size_t)N));
+    CK(download(d, n_trials, dntr, (size_t)N));
+    CK(download(d, n_iterations, dnit, (size_t)N));
+    CK(download(d, converged, dconv, (size_t)N));
+    CK(download(d, dense_exposures, dHd, NK));
+    CK(download(d, dense_errors, derr_d, (size_t)N));
+    CK(download(d, dense_n_iterations, dnit_d, (size_t)N));
+    CK(download(d, dense_converged, dconv_d, (size_t)N));
     HIPCK(hipStreamSynchronize(d.stream));
-    if (timings) {
-        for (int i = 0; i < 3; ++i) {
-            double total = 0.0;
-            for (const auto& pr : spans[i]) {
-                float ms = 0.f;
-                HIPCK(hipEventElapsedTime(&ms, pr.first, pr.second));
-                total += (double)ms;
-            }
-            timings[i] = total;
-        }
-        timings[3] = (double)n_chunks;
-    }
+    CK(sp.totals(3, timings));
+    if (timings) timings[3] = (double)n_chunks;
     return 0;
 }
 
@@ -525,22 +513,19 @@ extern "C" int salnmf_draw_model_counts(int device, const double* exposures, int
     hipDeviceProp_t prop;
     CK(open_device(device, &prop));
     const size_t NV = (size_t)N * V;
-    const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(B, ((int64_t)256 << 20) / (int64_t)(sizeof(double) * NV)));
+    const int chunk = (int)chunk_rows(0, sizeof(double) * NV, B);
     DevBufs d;
     CK(d.own_stream());
-    double* dH = d.get<double>((size_t)N * K);
-    double* dW = d.get<double>((size_t)K * V);
-    uint32_t* dT = d.get<uint32_t>((size_t)N);
+    double* dH = upload(d, exposures, (size_t)N * K);
+    double* dW = upload(d, signatures, (size_t)K * V);
+    uint32_t* dT = upload(d, trials);
     double* dout = d.get<double>((size_t)chunk * NV);
     if (!dH || !dW || !dT || !dout) return fail("hipMalloc failed (%d draws of %lld x %d)", chunk, (long long)N, V);
-    HIPCK(hipMemcpyAsync(dH, exposures, (size_t)N * K * sizeof(double), hipMemcpyHostToDevice, d.stream));
-    HIPCK(hipMemcpyAsync(dW, signatures, (size_t)K * V * sizeof(double), hipMemcpyHostToDevice, d.stream));
-    HIPCK(hipMemcpyAsync(dT, trials.data(), trials.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
     for (int first = 0; first < B; first += chunk) {
         const int count = std::min(chunk, B - first);
         gof_launch_model_draw(dH, dW, dT, nullptr, dout, N, V, K, seed, 0.0, first, count, d.stream);
         HIPCK(hipGetLastError());
-        HIPCK(hipMemcpyAsync(out + (size_t)first * NV, dout, (size_t)count * NV * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+        CK(download(d, out + (size_t)first * NV, dout, (size_t)count * NV));
     }
     HIPCK(hipStreamSynchronize(d.stream));
     return 0;
@@ -562,13 +547,12 @@ extern "C" int salnmf_goodness_of_fit(int device, const double* counts, int64_t 
     const size_t NV = (size_t)N * V, NK = (size_t)N * K, NB = (size_t)N * B;
 
     // draws per chunk: the [chunk][N][V] buffer stays within chunk_bytes (at least one draw)
-    const int64_t budget = chunk_bytes > 0 ? chunk_bytes : (int64_t)256 << 20;
-    const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(B, budget / (int64_t)(sizeof(double) * NV)));
+    const int chunk = (int)chunk_rows(chunk_bytes, sizeof(double) * NV, B);
 
     DevBufs d;
     CK(d.own_stream());
-    double* dW = d.get<double>((size_t)K * V);
-    double* dX = d.get<double>(NV);
+    double* dW = upload(d, signatures, (size_t)K * V);
+    double* dX = upload(d, in.x);
     double* dH = d.get<double>(NK);
     double* derr = d.get<double>((size_t)N);
     int* dnit = d.get<int>((size_t)N);
@@ -583,30 +567,21 @@ extern "C" int salnmf_goodness_of_fit(int device, const double* counts, int64_t 
     double* dmean = d.get<double>((size_t)N);
     if (!dW || !dX || !dH || !derr || !dnit || !dconv || !dnext || !dXb || !dHb || !derr_b || !dnit_b || !dconv_b || !dexceed || !dmean)
         return fail("hipMalloc failed (%d draws of %lld x %d, %d signatures)", B, (long long)N, V, K);
-    HIPCK(hipMemcpyAsync(dW, signatures, (size_t)K * V * sizeof(double), hipMemcpyHostToDevice, d.stream));
-    HIPCK(hipMemcpyAsync(dX, in.x.data(), NV * sizeof(double), hipMemcpyHostToDevice, d.stream));
 
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> spans[3];  // draw, refit, reduce
-    auto timed = [&](int which, auto&& body) -> int {
-        hipEvent_t e0 = timings ? d.mark() : nullptr;
-        CK(body());
-        hipEvent_t e1 = timings ? d.mark() : nullptr;
-        if (timings && (!e0 || !e1)) return fail("event record failed");
-        if (timings) spans[which].emplace_back(e0, e1);
-        return 0;
-    };
+    Spans sp;  // draw, refit, reduce
+    sp.start(d, timings != nullptr);
     const RefitArgs a{dX, dW, dH, derr, dnit, dconv, dnext, N, V, K, min_iterations, max_iterations, conv_test_freq, tol};
-    CK(timed(1, [&] { return launch_refit(a, cus, d.stream); }));
+    CK(sp.timed(1, [&] { return launch_refit(a, cus, d.stream); }));
     int n_chunks = 0;
     for (int first = 0; first < B; first += chunk, ++n_chunks) {
         const int count = std::min(chunk, B - first);
         // from the device-resident exposures of the observed refit; a row's trial count is read off the clipped counts
-        CK(timed(0, [&]() -> int {
+        CK(sp.timed(0, [&]() -> int {
             gof_launch_model_draw(dH, dW, nullptr, dX, dXb, N, V, K, seed, SALNMF_EPSILON, first, count, d.stream);
             HIPCK(hipGetLastError());
             return 0;
         }));
-        if (draws) HIPCK(hipMemcpyAsync(draws + (size_t)first * NV, dXb, (size_t)count * NV * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+        if (draws) CK(download(d, draws + (size_t)first * NV, dXb, (size_t)count * NV));
         RefitArgs c = a;
         c.X = dXb;
         c.P = (int64_t)count * N;
@@ -614,49 +589,41 @@ extern "C" int salnmf_goodness_of_fit(int device, const double* counts, int64_t 
         c.err = derr_b + (size_t)first * N;
         c.nit = dnit_b + (size_t)first * N;
         c.conv = dconv_b;
-        CK(timed(1, [&] { return launch_refit(c, cus, d.stream); }));
+        CK(sp.timed(1, [&] { return launch_refit(c, cus, d.stream); }));
     }
     const GofReduceArgs red{derr, derr_b, dexceed, dmean, N, B};
-    CK(timed(2, [&]() -> int {
+    CK(sp.timed(2, [&]() -> int {
         gof_launch_reduce(red, d.stream);
         HIPCK(hipGetLastError());
         return 0;
     }));
-    HIPCK(hipMemcpyAsync(exposures, dH, NK * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(errors, derr, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(n_iterations, dnit, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(converged, dconv, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(n_exceed, dexceed, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(null_mean, dmean, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(null_errors, derr_b, NB * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(null_n_iterations, dnit_b, NB * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    CK(download(d, exposures, dH, NK));
+    CK(download(d, errors, derr, (size_t)N));
+    CK(download(d, n_iterations, dnit, (size_t)N));
+    CK(download(d, converged, dconv, (size_t)N));
+    CK(download(d, n_exceed, dexceed, (size_t)N));
+    CK(download(d, null_mean, dmean, (size_t)N));
+    CK(download(d, null_errors, derr_b, NB));
+    CK(download(d, null_n_iterations, dnit_b, NB));
     HIPCK(hipStreamSynchronize(d.stream));
     if (draws)  // plain counts: the clipped zeros restored to 0
         for (size_t i = 0; i < (size_t)B * NV; ++i)
             if (draws[i] < 1.0) draws[i] = 0.0;
-    if (timings) {
-        for (int i = 0; i < 3; ++i) {
-            double total = 0.0;
-            for (const auto& pr : spans[i]) {
-                float ms = 0.f;
-                HIPCK(hipEventElapsedTime(&ms, pr.first, pr.second));
-                total += (double)ms;
-            }
-            timings[i] = total;
-        }
-        timings[3] = (double)n_chunks;
-    }
+    CK(sp.totals(3, timings));
+    if (timings) timings[3] = (double)n_chunks;
     return 0;
 }
 
-// ---- is signature s present?  A nested pair of fits against its own bootstrap null (salnmf_presence.h);
-// and could the test have seen it?  (salnmf_power.h).  Both entry points run presence_enqueue and
-// presence_finish; the power analysis puts its launches on the same stream in between.
+// ---- the pair run: what the presence test (salnmf_presence.h), its power analysis (salnmf_power.h, section
+// 18) and the profile likelihood with its intervals (salnmf_profile.h, section 19) do alike.  All four entry points run
+// pair_observed; the first two go on with their draws (presence_enqueue, pair_draw_solve) and presence_finish, the power
+// analysis putting its launches on the same stream in between; the last two wait (profile_observed), list their problems on
+// the host, run one profile_kernel launch and scatter its trials.
 
 namespace {
 
-// salnmf_signature_presence's arguments
-struct PresenceIO {
+// The arguments of a pair call.  The first group is every call's; the second the presence test's (null and 0 in a profile call).
+struct PairIO {
     int device;
     const double* counts;
     int64_t N;
@@ -666,57 +633,54 @@ struct PresenceIO {
     const int* test;
     int S;
     const uint8_t* candidates;
-    int B;
-    uint64_t seed;
     int min_iterations, max_iterations, conv_test_freq;
     double tol;
-    int64_t chunk_bytes;
     uint8_t* tested;
+    double *exposures, *errors;  // the alternative fit: (N, K) and (N)
+    double* timings;
+
+    int B;
+    uint64_t seed;
+    int64_t chunk_bytes;
     double* statistic;
     int* n_exceed;
-    double *null_mean, *exposures, *errors, *null_exposures, *null_errors;
+    double *null_mean, *null_exposures, *null_errors;
     int *n_iterations, *converged;
     double* null_statistics;
     int* null_n_iterations;
-    double *draws, *timings;
+    double* draws;
 };
 
-// What a call keeps between its launches and its results: the pair list, the device buffers and the host ends of the
-// asynchronous copies (which live until d's destructor has waited for the stream: d is the last member, and exists once the
-// validation has passed and a pair is tested).
-struct PresenceRun {
+// What a call keeps between its launches and its results: the pair list, the observed fits of every pair on the host (stat =
+// f0 - f1, f = (f1, f0), H1), the device buffers later launches read again and the host ends of the asynchronous copies (which
+// live until d's destructor has waited for the stream: d is the last member, and exists once the validation has passed and a
+// pair is tested).
+struct PairRun {
     RefitInputs in;
     std::vector<int> pair_n, pair_s;
     std::vector<size_t> slot;  // pair j is entry slot[j] of the (N, S) results
-    std::vector<double> h_stat, h_f, h_H1, h_H0, h_mean, h_stat_b, h_draws;
+    std::vector<double> h_stat, h_f, h_H1;
+    std::vector<double> h_H0, h_mean, h_stat_b, h_draws;  // the presence test's
     std::vector<int> h_nit, h_conv, h_exceed, h_nit_b;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> spans[7];  // draw, solve, reduce; planting, alternative draw, solve, reduce
+    Spans sp;  // presence: draw, solve, reduce; planting, alternative draw, solve, reduce.  profile: the observed launch, the profile launch
     size_t NP = 0;
     int64_t chunk_rows = 0;  // rows [pairs][V] of the chunk buffer that chunk_bytes allows
     int n_chunks = 0;
-    bool timing = false;
     double *dW = nullptr, *dX = nullptr, *dH0 = nullptr, *dstat_b = nullptr, *dXb = nullptr;
     int *dpn = nullptr, *dps = nullptr;
+    uint32_t* dcand = nullptr;
     PresenceArgs a{};  // the observed launch's
     std::unique_ptr<DevBufs> d;
 
-    template <typename F>
-    int timed(int which, F&& body) {
-        hipEvent_t e0 = timing ? d->mark() : nullptr;
-        CK(body());
-        hipEvent_t e1 = timing ? d->mark() : nullptr;
-        if (timing && (!e0 || !e1)) return fail("event record failed");
-        if (timing) spans[which].emplace_back(e0, e1);
-        return 0;
+    int launch_profile_kernel(const PairIO& io, ProfileArgs pa) {
+        pa.X = dX, pa.W = dW, pa.cand = dcand, pa.next_tile = a.next_tile;
+        pa.V = io.V, pa.K = io.K, pa.min_it = io.min_iterations, pa.max_it = io.max_iterations, pa.freq = io.conv_test_freq, pa.tol = io.tol;
+        return sp.timed(1, [&] { return launch_profile(pa, in.cus, d->stream); });
     }
-    int span_ms(int which, double* out) {
-        double total = 0.0;
-        for (const auto& pr : spans[which]) {
-            float ms = 0.f;
-            HIPCK(hipEventElapsedTime(&ms, pr.first, pr.second));
-            total += (double)ms;
-        }
-        *out = total;
+    // (after the stream has been waited for)
+    int profile_times(const PairIO& io, int64_t P) {
+        CK(sp.totals(2, io.timings));
+        if (io.timings) io.timings[2] = (double)P;
         return 0;
     }
 };
@@ -750,41 +714,115 @@ void presence_list_pairs(const RefitInputs& in, int64_t N, int K, const int* tes
     }
 }
 
+// What follows a call's own null checks: the rest of the validation (integer counts only where draws will be made of them), the
+// pair list, the untested entries of the alternative fit, and -- with a tested pair -- the uploads and the observed launch under
+// span `span`: the alternative solve on C, then the null solve (which is the frozen solve at 0.0), and the copies of stat, f and
+// H1 back.  Nothing is waited for; h0 (r.dH0, [pairs][K]) stays on the device.
+int pair_observed(const PairIO& io, bool integer_counts, int span, PairRun& r) {
+    const int64_t N = io.N;
+    const int V = io.V, K = io.K, S = io.S;
+    if (io.conv_test_freq >= 1 && io.max_iterations >= 0 && io.max_iterations % io.conv_test_freq != 0)
+        return fail("max_iterations must be a multiple of conv_test_freq, got %d and %d", io.max_iterations, io.conv_test_freq);
+    CK(presence_check_test(io.test, S, K));
+    RefitInputs& in = r.in;
+    CK(refit_prepare(io.device, io.counts, N, V, io.signatures, K, 0, 0, nullptr, io.min_iterations, io.max_iterations, io.conv_test_freq, io.tol, true,
+                     in, AssignSets{io.candidates, nullptr, 0}));
+    if (integer_counts) CK(refit_check_counts(io.counts, N, V, in.icounts));  // row totals below 2^32 too (the values themselves are not used)
+    presence_list_pairs(in, N, K, io.test, S, io.candidates != nullptr, io.tested, r.pair_n, r.pair_s, r.slot);
+    const size_t NP = r.NP = r.pair_n.size();
+    if (NP > 0x7fffffff) return fail("%zu tested pairs: at most 2^31 - 1", NP);
+    const double nan = std::nan("");
+    std::fill(io.exposures, io.exposures + (size_t)N * K, nan);
+    std::fill(io.errors, io.errors + N, nan);
+    if (NP == 0) return 0;
+
+    const size_t PK = NP * K;
+    r.h_stat.resize(NP), r.h_f.resize(2 * NP), r.h_H1.resize(PK);
+    r.d.reset(new DevBufs);
+    DevBufs& d = *r.d;
+    CK(d.own_stream());
+    r.dW = upload(d, io.signatures, (size_t)K * V);
+    r.dX = upload(d, in.x);
+    r.dpn = upload(d, r.pair_n);
+    r.dps = upload(d, r.pair_s);
+    r.dcand = io.candidates ? upload(d, in.cand) : nullptr;
+    double* dstat = d.get<double>(NP);
+    double* df = d.get<double>(2 * NP);
+    int* dnit = d.get<int>(2 * NP);
+    int* dconv = d.get<int>(2 * NP);
+    double* dH1 = d.get<double>(PK);
+    r.dH0 = d.get<double>(PK);
+    unsigned* dnext = d.get<unsigned>(1);
+    if (!r.dW || !r.dX || !r.dpn || !r.dps || !dstat || !df || !dnit || !dconv || !dH1 || !r.dH0 || !dnext || (io.candidates && !r.dcand))
+        return fail("hipMalloc or upload failed (%zu pairs x %d, %d signatures)", NP, V, K);
+    r.sp.start(d, io.timings != nullptr);
+    r.a = PresenceArgs{r.dX, r.dW, r.dpn, r.dps, r.dcand, dstat, dnit, df, dconv, dH1, r.dH0, dnext, (int64_t)NP, (int64_t)NP, V, K, 1,
+                       io.min_iterations, io.max_iterations, io.conv_test_freq, io.tol};
+    CK(r.sp.timed(span, [&] { return launch_presence(r.a, in.cus, d.stream); }));
+    CK(download(d, r.h_stat, dstat));
+    CK(download(d, r.h_f, df));
+    CK(download(d, r.h_H1, dH1));
+    return 0;
+}
+
+// (after the stream has been waited for) a sample's alternative fit is that of its first tested pair: every tested pair of a
+// sample solves the same problem on C and holds the same bits
+void pair_scatter_alternative(const PairIO& io, const PairRun& r) {
+    const int K = io.K;
+    for (size_t j = 0; j < r.NP; ++j)
+        if (j == 0 || r.pair_n[j - 1] != r.pair_n[j]) {
+            const size_t n = (size_t)r.pair_n[j];
+            std::copy(r.h_H1.begin() + j * K, r.h_H1.begin() + (j + 1) * K, io.exposures + n * K);
+            io.errors[n] = r.h_f[2 * j];
+        }
+}
+
+// Draw rows first .. of `rows` into the chunk buffer (draw(first, count) launches the draw of `count` rows [pairs][V] into
+// r.dXb), `chunk` at a time, and solve them as the observed launch solved the counts: a draw's problems keep their statistic
+// (stat [rows][pairs]) and iteration counts (nit [rows][pairs][2]) only.  host_copy, if not null, gets the drawn rows.
+template <typename Draw>
+int pair_draw_solve(PairRun& r, int64_t rows, int64_t chunk, Draw&& draw, double* stat, int* nit, double* host_copy, int span_draw, int span_solve,
+                    int* n_chunks) {
+    DevBufs& d = *r.d;
+    const size_t NP = r.NP, PV = NP * r.a.V;
+    for (int64_t first = 0; first < rows; first += chunk, ++*n_chunks) {
+        const int64_t count = std::min(chunk, rows - first);
+        CK(r.sp.timed(span_draw, [&]() -> int {
+            draw(first, count);
+            HIPCK(hipGetLastError());
+            return 0;
+        }));
+        if (host_copy) CK(download(d, host_copy + (size_t)first * PV, r.dXb, (size_t)count * PV));
+        PresenceArgs c = r.a;
+        c.X = r.dXb;
+        c.by_sample = 0;
+        c.P = count * (int64_t)NP;
+        c.stat = stat + (size_t)first * NP;
+        c.nit = nit + 2 * (size_t)first * NP;
+        c.f = nullptr, c.conv = nullptr, c.H1 = nullptr, c.H0 = nullptr;
+        CK(r.sp.timed(span_solve, [&] { return launch_presence(c, r.in.cus, d.stream); }));
+    }
+    return 0;
+}
+
 // Validation, the pair list, the untested entries of the results, and -- with a tested pair -- everything the presence test puts
-// on the stream: the uploads, the observed launch, the null chunks, the reduction and the downloads.  Nothing is waited for.  h0
-// (r.dH0, [pairs][K]) and the null statistics (r.dstat_b, [B][pairs]) stay on the device; the chunk buffer r.dXb holds
-// min(max(B, other_rows), r.chunk_rows) rows, so that a caller with other_rows draws of its own can reuse it.
-int presence_enqueue(const PresenceIO& io, int64_t other_rows, PresenceRun& r) {
+// on the stream: pair_observed, the null chunks, the reduction and the downloads.  Nothing is waited for.  The null statistics
+// (r.dstat_b, [B][pairs]) stay on the device; the chunk buffer r.dXb holds min(max(B, other_rows), r.chunk_rows) rows, so that a
+// caller with other_rows draws of its own can reuse it.
+int presence_enqueue(const PairIO& io, int64_t other_rows, PairRun& r) {
     const int64_t N = io.N;
     const int V = io.V, K = io.K, S = io.S, B = io.B;
-    const double* counts = io.counts;
-    const int* test = io.test;
-    const uint8_t* candidates = io.candidates;
-    if (!counts || !io.signatures || !test || !io.tested || !io.statistic || !io.n_exceed || !io.null_mean || !io.exposures || !io.errors ||
+    if (!io.counts || !io.signatures || !io.test || !io.tested || !io.statistic || !io.n_exceed || !io.null_mean || !io.exposures || !io.errors ||
         !io.null_exposures || !io.null_errors || !io.n_iterations || !io.converged || !io.null_statistics || !io.null_n_iterations)
         return fail("null argument");
     CK(gof_check_draws(B));
-    if (io.conv_test_freq >= 1 && io.max_iterations >= 0 && io.max_iterations % io.conv_test_freq != 0)
-        return fail("max_iterations must be a multiple of conv_test_freq, got %d and %d", io.max_iterations, io.conv_test_freq);
-    CK(presence_check_test(test, S, K));
-    RefitInputs& in = r.in;
-    CK(refit_prepare(io.device, counts, N, V, io.signatures, K, 0, 0, nullptr, io.min_iterations, io.max_iterations, io.conv_test_freq, io.tol, true, in,
-                     AssignSets{candidates, nullptr, 0}));
-    CK(refit_check_counts(counts, N, V, in.icounts));  // integer counts, row totals below 2^32 (the values themselves are not used)
-    const int cus = in.cus;
-
-    const size_t NS = (size_t)N * S, NV = (size_t)N * V, NK = (size_t)N * K;
-    std::vector<int>&pair_n = r.pair_n, &pair_s = r.pair_s;
-    presence_list_pairs(in, N, K, test, S, candidates != nullptr, io.tested, pair_n, pair_s, r.slot);
-    const size_t NP = pair_n.size();
-    if (NP > 0x7fffffff) return fail("%zu tested pairs: at most 2^31 - 1", NP);
+    CK(pair_observed(io, true, 1, r));
+    const size_t NS = (size_t)N * S, NP = r.NP;
     const double nan = std::nan("");
     std::fill(io.statistic, io.statistic + NS, nan);
     std::fill(io.null_mean, io.null_mean + NS, nan);
     std::fill(io.null_errors, io.null_errors + NS, nan);
     std::fill(io.n_exceed, io.n_exceed + NS, 0);
-    std::fill(io.exposures, io.exposures + NK, nan);
-    std::fill(io.errors, io.errors + N, nan);
     std::fill(io.null_exposures, io.null_exposures + NS * K, nan);
     std::fill(io.n_iterations, io.n_iterations + 2 * NS, 0);
     std::fill(io.converged, io.converged + 2 * NS, 0);
@@ -792,111 +830,56 @@ int presence_enqueue(const PresenceIO& io, int64_t other_rows, PresenceRun& r) {
     std::fill(io.null_n_iterations, io.null_n_iterations + 2 * (size_t)B * NS, 0);
     if (io.draws) std::fill(io.draws, io.draws + (size_t)B * NS * V, 0.0);
     if (io.timings) io.timings[0] = io.timings[1] = io.timings[2] = io.timings[3] = 0.0;
-    r.NP = NP;
     if (NP == 0) return 0;
 
     // draws per chunk: the [chunk][pairs][V] buffer stays within chunk_bytes (at least one draw)
     const size_t PV = NP * V, PK = NP * K, PB = NP * B;
-    const int64_t budget = io.chunk_bytes > 0 ? io.chunk_bytes : (int64_t)256 << 20;
-    r.chunk_rows = std::max<int64_t>(1, budget / (int64_t)(sizeof(double) * PV));
-    const int chunk = (int)std::min<int64_t>(B, r.chunk_rows);
+    r.chunk_rows = chunk_rows(io.chunk_bytes, sizeof(double) * PV, INT64_MAX);
     const int64_t buffer_rows = std::min<int64_t>(std::max<int64_t>(B, other_rows), r.chunk_rows);
-
-    r.h_stat.resize(NP), r.h_f.resize(2 * NP), r.h_H1.resize(PK), r.h_H0.resize(PK), r.h_mean.resize(NP), r.h_stat_b.resize(PB);
-    r.h_draws.resize(io.draws ? PB * V : 0);
+    r.h_H0.resize(PK), r.h_mean.resize(NP), r.h_stat_b.resize(PB), r.h_draws.resize(io.draws ? PB * V : 0);
     r.h_nit.resize(2 * NP), r.h_conv.resize(2 * NP), r.h_exceed.resize(NP), r.h_nit_b.resize(2 * PB);
-    r.d.reset(new DevBufs);
     DevBufs& d = *r.d;
-    CK(d.own_stream());
-    double* dW = r.dW = d.get<double>((size_t)K * V);
-    double* dX = r.dX = d.get<double>(NV);
-    int* dpn = r.dpn = d.get<int>(NP);
-    int* dps = r.dps = d.get<int>(NP);
-    double* dstat = d.get<double>(NP);
-    double* df = d.get<double>(2 * NP);
-    int* dnit = d.get<int>(2 * NP);
-    int* dconv = d.get<int>(2 * NP);
-    double* dH1 = d.get<double>(PK);
-    double* dH0 = r.dH0 = d.get<double>(PK);
-    unsigned* dnext = d.get<unsigned>(1);
-    double* dXb = r.dXb = d.get<double>((size_t)buffer_rows * PV);
-    double* dstat_b = r.dstat_b = d.get<double>(PB);
+    r.dXb = d.get<double>((size_t)buffer_rows * PV);
+    r.dstat_b = d.get<double>(PB);
     int* dnit_b = d.get<int>(2 * PB);
     int* dexceed = d.get<int>(NP);
     double* dmean = d.get<double>(NP);
-    uint32_t* dcand = candidates ? d.get<uint32_t>(in.cand.size()) : nullptr;
-    if (!dW || !dX || !dpn || !dps || !dstat || !df || !dnit || !dconv || !dH1 || !dH0 || !dnext || !dXb || !dstat_b || !dnit_b || !dexceed || !dmean ||
-        (candidates && !dcand))
-        return fail("hipMalloc failed (%d draws of %zu pairs x %d, %d signatures)", B, NP, V, K);
-    HIPCK(hipMemcpyAsync(dW, io.signatures, (size_t)K * V * sizeof(double), hipMemcpyHostToDevice, d.stream));
-    HIPCK(hipMemcpyAsync(dX, in.x.data(), NV * sizeof(double), hipMemcpyHostToDevice, d.stream));
-    HIPCK(hipMemcpyAsync(dpn, pair_n.data(), NP * sizeof(int), hipMemcpyHostToDevice, d.stream));
-    HIPCK(hipMemcpyAsync(dps, pair_s.data(), NP * sizeof(int), hipMemcpyHostToDevice, d.stream));
-    if (dcand) HIPCK(hipMemcpyAsync(dcand, in.cand.data(), in.cand.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
-
-    r.timing = io.timings != nullptr;
-    const PresenceArgs a = r.a = PresenceArgs{dX, dW, dpn, dps, dcand, dstat, dnit, df, dconv, dH1, dH0, dnext, (int64_t)NP, (int64_t)NP, V, K, 1,
-                                              io.min_iterations, io.max_iterations, io.conv_test_freq, io.tol};
-    CK(r.timed(1, [&] { return launch_presence(a, cus, d.stream); }));
-    for (int first = 0; first < B; first += chunk, ++r.n_chunks) {
-        const int count = std::min(chunk, B - first);
-        // from the device-resident exposures of the observed null fits; a row's trial count is read off the clipped counts
-        CK(r.timed(0, [&]() -> int {
-            presence_launch_draw(dH0, dW, dX, dpn, dps, dXb, (int64_t)NP, V, K, io.seed, SALNMF_EPSILON, first, count, d.stream);
-            HIPCK(hipGetLastError());
-            return 0;
-        }));
-        if (io.draws)
-            HIPCK(hipMemcpyAsync(r.h_draws.data() + (size_t)first * PV, dXb, (size_t)count * PV * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-        // a draw's problems keep their statistic and iteration counts only
-        PresenceArgs c = a;
-        c.X = dXb;
-        c.by_sample = 0;
-        c.P = (int64_t)count * (int64_t)NP;
-        c.stat = dstat_b + (size_t)first * NP;
-        c.nit = dnit_b + 2 * (size_t)first * NP;
-        c.f = nullptr, c.conv = nullptr, c.H1 = nullptr, c.H0 = nullptr;
-        CK(r.timed(1, [&] { return launch_presence(c, cus, d.stream); }));
-    }
+    if (!r.dXb || !r.dstat_b || !dnit_b || !dexceed || !dmean) return fail("hipMalloc failed (%d draws of %zu pairs x %d, %d signatures)", B, NP, V, K);
+    // from the device-resident exposures of the observed null fits; a row's trial count is read off the clipped counts
+    CK(pair_draw_solve(r, B, std::min<int64_t>(B, r.chunk_rows), [&](int64_t first, int64_t count) {
+        presence_launch_draw(r.dH0, r.dW, r.dX, r.dpn, r.dps, r.dXb, (int64_t)NP, V, K, io.seed, SALNMF_EPSILON, (int)first, (int)count, d.stream);
+    }, r.dstat_b, dnit_b, io.draws ? r.h_draws.data() : nullptr, 0, 1, &r.n_chunks));
     // gof_reduce_kernel over the pairs: n_exceed counts t_b >= t (false for a NaN on either side), null_mean sums from 0.0 in ascending b
-    const GofReduceArgs red{dstat, dstat_b, dexceed, dmean, (int64_t)NP, B};
-    CK(r.timed(2, [&]() -> int {
+    const GofReduceArgs red{r.a.stat, r.dstat_b, dexceed, dmean, (int64_t)NP, B};
+    CK(r.sp.timed(2, [&]() -> int {
         gof_launch_reduce(red, d.stream);
         HIPCK(hipGetLastError());
         return 0;
     }));
-    HIPCK(hipMemcpyAsync(r.h_stat.data(), dstat, NP * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(r.h_f.data(), df, 2 * NP * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(r.h_nit.data(), dnit, 2 * NP * sizeof(int), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(r.h_conv.data(), dconv, 2 * NP * sizeof(int), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(r.h_H1.data(), dH1, PK * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(r.h_H0.data(), dH0, PK * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(r.h_exceed.data(), dexceed, NP * sizeof(int), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(r.h_mean.data(), dmean, NP * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(r.h_stat_b.data(), dstat_b, PB * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(r.h_nit_b.data(), dnit_b, 2 * PB * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    CK(download(d, r.h_nit, r.a.nit));
+    CK(download(d, r.h_conv, r.a.conv));
+    CK(download(d, r.h_H0, r.dH0));
+    CK(download(d, r.h_exceed, dexceed));
+    CK(download(d, r.h_mean, dmean));
+    CK(download(d, r.h_stat_b, r.dstat_b));
+    CK(download(d, r.h_nit_b, dnit_b));
     return 0;
 }
 
 // Waits for the stream, then the compact pair list back into the (N, S) results and the first four timings.
-int presence_finish(const PresenceIO& io, PresenceRun& r) {
+int presence_finish(const PairIO& io, PairRun& r) {
     const int V = io.V, K = io.K, B = io.B;
     const size_t NP = r.NP, NS = (size_t)io.N * io.S;
     HIPCK(hipStreamSynchronize(r.d->stream));
-    // a sample's alternative fit is that of its first tested pair (every tested pair of a sample solves the same problem on C and
-    // holds the same bits)
+    pair_scatter_alternative(io, r);
     for (size_t j = 0; j < NP; ++j) {
-        const size_t o = r.slot[j], n = (size_t)r.pair_n[j];
+        const size_t o = r.slot[j];
         io.statistic[o] = r.h_stat[j];
         io.n_exceed[o] = r.h_exceed[j];
         io.null_mean[o] = r.h_mean[j];
         io.null_errors[o] = r.h_f[2 * j + 1];
         std::copy(r.h_H0.begin() + j * K, r.h_H0.begin() + (j + 1) * K, io.null_exposures + o * K);
         for (int i = 0; i < 2; ++i) io.n_iterations[2 * o + i] = r.h_nit[2 * j + i], io.converged[2 * o + i] = r.h_conv[2 * j + i];
-        if (j == 0 || (size_t)r.pair_n[j - 1] != n) {
-            std::copy(r.h_H1.begin() + j * K, r.h_H1.begin() + (j + 1) * K, io.exposures + n * K);
-            io.errors[n] = r.h_f[2 * j];
-        }
         for (size_t b = 0; b < (size_t)B; ++b) {
             io.null_statistics[b * NS + o] = r.h_stat_b[b * NP + j];
             for (int i = 0; i < 2; ++i) io.null_n_iterations[2 * (b * NS + o) + i] = r.h_nit_b[2 * (b * NP + j) + i];
@@ -907,10 +890,20 @@ int presence_finish(const PresenceIO& io, PresenceRun& r) {
                 }
         }
     }
-    if (io.timings) {
-        for (int i = 0; i < 3; ++i) CK(r.span_ms(i, io.timings + i));
-        io.timings[3] = (double)r.n_chunks;
-    }
+    CK(r.sp.totals(3, io.timings));
+    if (io.timings) io.timings[3] = (double)r.n_chunks;
+    return 0;
+}
+
+// The profile calls' start: pair_observed (the counts need not be integers: nothing is drawn), waited for, and the alternative
+// fit scattered.
+int profile_observed(const PairIO& io, PairRun& r) {
+    if (!io.counts || !io.signatures || !io.test || !io.tested || !io.exposures || !io.errors) return fail("null argument");
+    CK(pair_observed(io, false, 0, r));
+    if (io.timings) io.timings[0] = io.timings[1] = io.timings[2] = 0.0;
+    if (r.NP == 0) return 0;
+    HIPCK(hipStreamSynchronize(r.d->stream));
+    pair_scatter_alternative(io, r);
     return 0;
 }
 
@@ -922,10 +915,10 @@ extern "C" int salnmf_signature_presence(int device, const double* counts, int64
                                          int* n_exceed, double* null_mean, double* exposures, double* errors, double* null_exposures, double* null_errors,
                                          int* n_iterations, int* converged, double* null_statistics, int* null_n_iterations, double* draws,
                                          double* timings) {
-    const PresenceIO io{device, counts, n_samples, n_features, signatures, n_signatures, test, n_test, candidates, n_draws, seed, min_iterations,
-                        max_iterations, conv_test_freq, tol, chunk_bytes, tested, statistic, n_exceed, null_mean, exposures, errors, null_exposures,
-                        null_errors, n_iterations, converged, null_statistics, null_n_iterations, draws, timings};
-    PresenceRun r;
+    const PairIO io{device, counts, n_samples, n_features, signatures, n_signatures, test, n_test, candidates, min_iterations, max_iterations,
+                    conv_test_freq, tol, tested, exposures, errors, timings, n_draws, seed, chunk_bytes, statistic, n_exceed, null_mean, null_exposures,
+                    null_errors, n_iterations, converged, null_statistics, null_n_iterations, draws};
+    PairRun r;
     CK(presence_enqueue(io, 0, r));
     if (r.NP == 0) return 0;
     return presence_finish(io, r);
@@ -951,12 +944,12 @@ extern "C" int salnmf_signature_power(int device, const double* counts, int64_t 
     if (A < 1 || A > POWER_MAX_DRAWS) return fail("n_alt_draws must be in [1, %d], got %d", POWER_MAX_DRAWS, A);
     if (max_exceed < 0 || max_exceed > B) return fail("max_exceed must be in [0, %d], got %d", B, max_exceed);
     const int64_t R = (int64_t)L * A;  // rows r = l A + a
-    const PresenceIO io{device, counts, n_samples, n_features, signatures, n_signatures, test, n_test, candidates, n_draws, seed, min_iterations,
-                        max_iterations, conv_test_freq, tol, chunk_bytes, tested, statistic, n_exceed, null_mean, exposures, errors, null_exposures,
-                        null_errors, n_iterations, converged, null_statistics, null_n_iterations, draws, timings};
+    const PairIO io{device, counts, n_samples, n_features, signatures, n_signatures, test, n_test, candidates, min_iterations, max_iterations,
+                    conv_test_freq, tol, tested, exposures, errors, timings, n_draws, seed, chunk_bytes, statistic, n_exceed, null_mean, null_exposures,
+                    null_errors, n_iterations, converged, null_statistics, null_n_iterations, draws};
     std::vector<double> h_Hp, h_stat_a, h_mean_a, h_draws_a;  // (before r: they outlive the copies into them, which r.d waits for)
     std::vector<int> h_nit_a, h_exceed_a, h_ndet;
-    PresenceRun r;
+    PairRun r;
     CK(presence_enqueue(io, R, r));
     const int64_t N = n_samples;
     const int V = n_features, K = n_signatures, S = n_test;
@@ -976,7 +969,7 @@ extern "C" int salnmf_signature_power(int device, const double* counts, int64_t 
     DevBufs& d = *r.d;
     h_Hp.resize((size_t)L * PK), h_stat_a.resize((size_t)R * NP), h_mean_a.resize((size_t)L * NP), h_draws_a.resize(alt_draws ? (size_t)R * PV : 0);
     h_nit_a.resize(2 * (size_t)R * NP), h_exceed_a.resize((size_t)R * NP), h_ndet.resize((size_t)L * NP);
-    double* dshares = d.get<double>((size_t)L);
+    double* dshares = upload(d, shares, (size_t)L);
     double* dHp = d.get<double>((size_t)L * PK);
     double* dstat_a = d.get<double>((size_t)R * NP);
     int* dnit_a = d.get<int>(2 * (size_t)R * NP);
@@ -984,45 +977,28 @@ extern "C" int salnmf_signature_power(int device, const double* counts, int64_t 
     int* dndet = d.get<int>((size_t)L * NP);
     double* dmean_a = d.get<double>((size_t)L * NP);
     if (!dshares || !dHp || !dstat_a || !dnit_a || !dexceed_a || !dndet || !dmean_a)
-        return fail("hipMalloc failed (%d shares x %d draws of %zu pairs x %d, %d signatures)", L, A, NP, V, K);
-    HIPCK(hipMemcpyAsync(dshares, shares, (size_t)L * sizeof(double), hipMemcpyHostToDevice, d.stream));
-    CK(r.timed(3, [&]() -> int {
+        return fail("hipMalloc or upload failed (%d shares x %d draws of %zu pairs x %d, %d signatures)", L, A, NP, V, K);
+    CK(r.sp.timed(3, [&]() -> int {
         power_launch_plant(PowerPlantArgs{r.dH0, r.dps, dshares, dHp, (int64_t)NP, K, L}, d.stream);
         HIPCK(hipGetLastError());
         return 0;
     }));
     // rows per chunk: the presence test's buffer and rule
-    const int64_t chunk = std::min<int64_t>(R, r.chunk_rows);
     int n_chunks = 0;
-    for (int64_t first = 0; first < R; first += chunk, ++n_chunks) {
-        const int64_t count = std::min(chunk, R - first);
-        CK(r.timed(4, [&]() -> int {
-            power_launch_draw(dHp, r.dW, r.dX, r.dpn, r.dps, r.dXb, (int64_t)NP, V, K, seed, SALNMF_EPSILON, A, first, count, d.stream);
-            HIPCK(hipGetLastError());
-            return 0;
-        }));
-        if (alt_draws)
-            HIPCK(hipMemcpyAsync(h_draws_a.data() + (size_t)first * PV, r.dXb, (size_t)count * PV * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-        PresenceArgs c = r.a;  // as a null draw's launch
-        c.X = r.dXb;
-        c.by_sample = 0;
-        c.P = count * (int64_t)NP;
-        c.stat = dstat_a + (size_t)first * NP;
-        c.nit = dnit_a + 2 * (size_t)first * NP;
-        c.f = nullptr, c.conv = nullptr, c.H1 = nullptr, c.H0 = nullptr;
-        CK(r.timed(5, [&] { return launch_presence(c, r.in.cus, d.stream); }));
-    }
-    CK(r.timed(6, [&]() -> int {
+    CK(pair_draw_solve(r, R, std::min<int64_t>(R, r.chunk_rows), [&](int64_t first, int64_t count) {
+        power_launch_draw(dHp, r.dW, r.dX, r.dpn, r.dps, r.dXb, (int64_t)NP, V, K, seed, SALNMF_EPSILON, A, first, count, d.stream);
+    }, dstat_a, dnit_a, alt_draws ? h_draws_a.data() : nullptr, 4, 5, &n_chunks));
+    CK(r.sp.timed(6, [&]() -> int {
         power_launch_reduce(PowerReduceArgs{r.dstat_b, dstat_a, dexceed_a, dndet, dmean_a, (int64_t)NP, B, L, A, max_exceed}, d.stream);
         HIPCK(hipGetLastError());
         return 0;
     }));
-    HIPCK(hipMemcpyAsync(h_Hp.data(), dHp, h_Hp.size() * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(h_stat_a.data(), dstat_a, h_stat_a.size() * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(h_nit_a.data(), dnit_a, h_nit_a.size() * sizeof(int), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(h_exceed_a.data(), dexceed_a, h_exceed_a.size() * sizeof(int), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(h_ndet.data(), dndet, h_ndet.size() * sizeof(int), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(h_mean_a.data(), dmean_a, h_mean_a.size() * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    CK(download(d, h_Hp.data(), dHp, h_Hp.size()));
+    CK(download(d, h_stat_a.data(), dstat_a, h_stat_a.size()));
+    CK(download(d, h_nit_a.data(), dnit_a, h_nit_a.size()));
+    CK(download(d, h_exceed_a.data(), dexceed_a, h_exceed_a.size()));
+    CK(download(d, h_ndet.data(), dndet, h_ndet.size()));
+    CK(download(d, h_mean_a.data(), dmean_a, h_mean_a.size()));
     CK(presence_finish(io, r));  // waits for the stream
 
     for (size_t j = 0; j < NP; ++j) {
@@ -1044,145 +1020,11 @@ extern "C" int salnmf_signature_power(int device, const double* counts, int64_t 
         }
     }
     if (timings) {
-        for (int i = 3; i < 7; ++i) CK(r.span_ms(i, timings + i + 1));
+        for (int i = 3; i < 7; ++i) CK(r.sp.total_ms(i, timings + i + 1));
         timings[8] = (double)n_chunks;
     }
     return 0;
 }
-
-// ---- the profile likelihood of one exposure and the interval it gives (salnmf_profile.h).  Both entry
-// points run profile_observed -- the presence test's observed launch, unchanged -- then list their problems on the host, run one
-// profile_kernel launch and scatter its trials.
-
-namespace {
-
-struct ProfileIO {
-    int device;
-    const double* counts;
-    int64_t N;
-    int V;
-    const double* signatures;
-    int K;
-    const int* test;
-    int S;
-    const uint8_t* candidates;
-    int min_iterations, max_iterations, conv_test_freq;
-    double tol;
-    uint8_t* tested;
-    double *exposures, *errors;  // the alternative fit: (N, K) and (N)
-    double* timings;
-};
-
-// The pair list, the observed fits of every pair on the host (stat = f0 - f1, f = (f1, f0), H1) and the device buffers the
-// profile launch reads again.  d is the last member: its destructor waits for the stream before the vectors go.
-struct ProfileRun {
-    RefitInputs in;
-    std::vector<int> pair_n, pair_s;
-    std::vector<size_t> slot;
-    std::vector<double> h_stat, h_f, h_H1;
-    size_t NP = 0;
-    double *dW = nullptr, *dX = nullptr;
-    uint32_t* dcand = nullptr;
-    unsigned* dnext = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // around the observed launch, around the profile launch
-    std::unique_ptr<DevBufs> d;
-
-    int launch(const ProfileIO& io, ProfileArgs a) {
-        a.X = dX, a.W = dW, a.cand = dcand, a.next_tile = dnext;
-        a.V = io.V, a.K = io.K, a.min_it = io.min_iterations, a.max_it = io.max_iterations, a.freq = io.conv_test_freq, a.tol = io.tol;
-        ev[2] = io.timings ? d->mark() : nullptr;
-        CK(launch_profile(a, in.cus, d->stream));
-        ev[3] = io.timings ? d->mark() : nullptr;
-        if (io.timings && (!ev[2] || !ev[3])) return fail("event record failed");
-        return 0;
-    }
-    // (after the stream has been waited for)
-    int times(const ProfileIO& io, int64_t P) {
-        if (!io.timings) return 0;
-        float ms = 0.f;
-        HIPCK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        io.timings[0] = (double)ms;
-        HIPCK(hipEventElapsedTime(&ms, ev[2], ev[3]));
-        io.timings[1] = (double)ms;
-        io.timings[2] = (double)P;
-        return 0;
-    }
-};
-
-// Validation, the pair list, the untested entries of the shared results, and -- with a tested pair -- the observed launch of
-// salnmf_signature_presence (the same PresenceArgs: the alternative solve on C, then the null solve, which is the frozen solve
-// at 0.0), waited for and copied back.  The counts need not be integers: nothing is drawn.
-int profile_observed(const ProfileIO& io, ProfileRun& r) {
-    const int64_t N = io.N;
-    const int V = io.V, K = io.K, S = io.S;
-    if (!io.counts || !io.signatures || !io.test || !io.tested || !io.exposures || !io.errors) return fail("null argument");
-    if (io.conv_test_freq >= 1 && io.max_iterations >= 0 && io.max_iterations % io.conv_test_freq != 0)
-        return fail("max_iterations must be a multiple of conv_test_freq, got %d and %d", io.max_iterations, io.conv_test_freq);
-    CK(presence_check_test(io.test, S, K));
-    RefitInputs& in = r.in;
-    CK(refit_prepare(io.device, io.counts, N, V, io.signatures, K, 0, 0, nullptr, io.min_iterations, io.max_iterations, io.conv_test_freq, io.tol, true,
-                     in, AssignSets{io.candidates, nullptr, 0}));
-    presence_list_pairs(in, N, K, io.test, S, io.candidates != nullptr, io.tested, r.pair_n, r.pair_s, r.slot);
-    const size_t NP = r.NP = r.pair_n.size();
-    if (NP > 0x7fffffff) return fail("%zu tested pairs: at most 2^31 - 1", NP);
-    const double nan = std::nan("");
-    std::fill(io.exposures, io.exposures + (size_t)N * K, nan);
-    std::fill(io.errors, io.errors + N, nan);
-    if (io.timings) io.timings[0] = io.timings[1] = io.timings[2] = 0.0;
-    if (NP == 0) return 0;
-
-    const size_t PK = NP * K, NV = (size_t)N * V;
-    r.h_stat.resize(NP), r.h_f.resize(2 * NP), r.h_H1.resize(PK);
-    r.d.reset(new DevBufs);
-    DevBufs& d = *r.d;
-    CK(d.own_stream());
-    double* dW = r.dW = d.get<double>((size_t)K * V);
-    double* dX = r.dX = d.get<double>(NV);
-    int* dpn = d.get<int>(NP);
-    int* dps = d.get<int>(NP);
-    double* dstat = d.get<double>(NP);
-    double* df = d.get<double>(2 * NP);
-    int* dnit = d.get<int>(2 * NP);
-    int* dconv = d.get<int>(2 * NP);
-    double* dH1 = d.get<double>(PK);
-    double* dH0 = d.get<double>(PK);
-    unsigned* dnext = r.dnext = d.get<unsigned>(1);
-    uint32_t* dcand = r.dcand = io.candidates ? d.get<uint32_t>(in.cand.size()) : nullptr;
-    if (!dW || !dX || !dpn || !dps || !dstat || !df || !dnit || !dconv || !dH1 || !dH0 || !dnext || (io.candidates && !dcand))
-        return fail("hipMalloc failed (%zu pairs x %d, %d signatures)", NP, V, K);
-    HIPCK(hipMemcpyAsync(dW, io.signatures, (size_t)K * V * sizeof(double), hipMemcpyHostToDevice, d.stream));
-    HIPCK(hipMemcpyAsync(dX, in.x.data(), NV * sizeof(double), hipMemcpyHostToDevice, d.stream));
-    HIPCK(hipMemcpyAsync(dpn, r.pair_n.data(), NP * sizeof(int), hipMemcpyHostToDevice, d.stream));
-    HIPCK(hipMemcpyAsync(dps, r.pair_s.data(), NP * sizeof(int), hipMemcpyHostToDevice, d.stream));
-    if (dcand) HIPCK(hipMemcpyAsync(dcand, in.cand.data(), in.cand.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
-    const PresenceArgs a{dX, dW, dpn, dps, dcand, dstat, dnit, df, dconv, dH1, dH0, dnext, (int64_t)NP, (int64_t)NP, V, K, 1,
-                         io.min_iterations, io.max_iterations, io.conv_test_freq, io.tol};
-    r.ev[0] = io.timings ? d.mark() : nullptr;
-    CK(launch_presence(a, in.cus, d.stream));
-    r.ev[1] = io.timings ? d.mark() : nullptr;
-    if (io.timings && (!r.ev[0] || !r.ev[1])) return fail("event record failed");
-    HIPCK(hipMemcpyAsync(r.h_stat.data(), dstat, NP * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(r.h_f.data(), df, 2 * NP * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(r.h_H1.data(), dH1, PK * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipStreamSynchronize(d.stream));
-    // a sample's alternative fit is that of its first tested pair (presence_finish)
-    for (size_t j = 0; j < NP; ++j)
-        if (j == 0 || r.pair_n[j - 1] != r.pair_n[j]) {
-            const size_t n = (size_t)r.pair_n[j];
-            std::copy(r.h_H1.begin() + j * K, r.h_H1.begin() + (j + 1) * K, io.exposures + n * K);
-            io.errors[n] = r.h_f[2 * j];
-        }
-    return 0;
-}
-
-template <typename T>
-T* profile_upload(DevBufs& d, const std::vector<T>& host) {
-    T* dev = d.get<T>(host.size());
-    if (dev && hipMemcpyAsync(dev, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice, d.stream) != hipSuccess) return nullptr;
-    return dev;
-}
-
-}  // namespace
 
 extern "C" int salnmf_profile_likelihood(int device, const double* counts, int64_t n_samples, int n_features, const double* signatures, int n_signatures,
                                          const int* test, int n_test, const uint8_t* candidates, const double* values, int n_values, int values_per_pair,
@@ -1199,12 +1041,12 @@ extern "C" int salnmf_profile_likelihood(int device, const double* counts, int64
     const size_t NS = (size_t)N * S, n_given = values_per_pair ? NS * M : (size_t)M;
     for (size_t i = 0; i < n_given; ++i)
         if (!std::isfinite(values[i]) || values[i] < 0.0) return fail("values must be finite and not negative: entry %zu holds %g", i, values[i]);
-    const ProfileIO io{device, counts, N, n_features, signatures, K, test, S, candidates, min_iterations, max_iterations, conv_test_freq, tol, tested,
-                       exposures, errors, timings};
+    const PairIO io{device, counts, N, n_features, signatures, K, test, S, candidates, min_iterations, max_iterations, conv_test_freq, tol, tested,
+                    exposures, errors, timings, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     // (before r: they outlive the copies into and out of them, which r.d waits for)
     std::vector<int> prob_n, prob_s, count, h_nit, h_conv;
     std::vector<double> vals, h_f, h_H;
-    ProfileRun r;
+    PairRun r;
     CK(profile_observed(io, r));
     const double nan = std::nan("");
     std::fill(profile, profile + NS * M, nan);
@@ -1230,17 +1072,17 @@ extern "C" int salnmf_profile_likelihood(int device, const double* counts, int64
     h_f.resize(P * T), h_nit.resize(P * T), h_conv.resize(P * T), h_H.resize(profile_exposures ? P * T * K : 0);
     DevBufs& d = *r.d;
     ProfileArgs a{};
-    a.prob_n = profile_upload(d, prob_n), a.prob_s = profile_upload(d, prob_s), a.count = profile_upload(d, count), a.values = profile_upload(d, vals);
+    a.prob_n = upload(d, prob_n), a.prob_s = upload(d, prob_s), a.count = upload(d, count), a.values = upload(d, vals);
     a.trial_f = d.get<double>(P * T), a.trial_nit = d.get<int>(P * T), a.trial_conv = d.get<int>(P * T);
     a.trial_H = profile_exposures ? d.get<double>(P * T * K) : nullptr;
     if (!a.prob_n || !a.prob_s || !a.count || !a.values || !a.trial_f || !a.trial_nit || !a.trial_conv || (profile_exposures && !a.trial_H))
         return fail("hipMalloc or upload failed (%zu problems of %d values, %d signatures)", P, T, K);
     a.P = (int64_t)P, a.T = T;
-    CK(r.launch(io, a));
-    HIPCK(hipMemcpyAsync(h_f.data(), a.trial_f, h_f.size() * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(h_nit.data(), a.trial_nit, h_nit.size() * sizeof(int), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(h_conv.data(), a.trial_conv, h_conv.size() * sizeof(int), hipMemcpyDeviceToHost, d.stream));
-    if (a.trial_H) HIPCK(hipMemcpyAsync(h_H.data(), a.trial_H, h_H.size() * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+    CK(r.launch_profile_kernel(io, a));
+    CK(download(d, h_f.data(), a.trial_f, h_f.size()));
+    CK(download(d, h_nit.data(), a.trial_nit, h_nit.size()));
+    CK(download(d, h_conv.data(), a.trial_conv, h_conv.size()));
+    if (a.trial_H) CK(download(d, h_H.data(), a.trial_H, h_H.size()));
     HIPCK(hipStreamSynchronize(d.stream));
     for (size_t p = 0; p < P; ++p) {
         const size_t j = p / runs, run = p % runs;
@@ -1252,7 +1094,7 @@ extern "C" int salnmf_profile_likelihood(int device, const double* counts, int64
             if (profile_exposures) std::copy(h_H.begin() + from * K, h_H.begin() + (from + 1) * K, profile_exposures + to * K);
         }
     }
-    return r.times(io, (int64_t)P);
+    return r.profile_times(io, (int64_t)P);
 }
 
 extern "C" int salnmf_exposure_intervals(int device, const double* counts, int64_t n_samples, int n_features, const double* signatures, int n_signatures,
@@ -1271,12 +1113,12 @@ extern "C" int salnmf_exposure_intervals(int device, const double* counts, int64
     if (E < 1 || E > PROFILE_MAX_EXPANSIONS) return fail("max_expansions must be in [1, %d], got %d", PROFILE_MAX_EXPANSIONS, E);
     if (N < 1 || N > 0x7fffffff) return fail("n_samples must be in [1, 2^31), got %lld", (long long)N);
     if (S < 1 || S > REFIT_KMAX) return fail("n_test must be in [1, %d], got %d", REFIT_KMAX, S);
-    const ProfileIO io{device, counts, N, n_features, signatures, K, test, S, candidates, min_iterations, max_iterations, conv_test_freq, tol, tested,
-                       exposures, errors, timings};
+    const PairIO io{device, counts, N, n_features, signatures, K, test, S, candidates, min_iterations, max_iterations, conv_test_freq, tol, tested,
+                    exposures, errors, timings, 0, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     std::vector<int> prob_n, prob_s, end, h_nt, h_br;
     std::vector<double> hhat, f1, h_c, h_f, h_lo, h_hi;
     std::vector<size_t> prob_pair;
-    ProfileRun r;
+    PairRun r;
     CK(profile_observed(io, r));
     const int T = E + J;
     const size_t NS = (size_t)N * S, NP = r.NP;
@@ -1303,21 +1145,21 @@ extern "C" int salnmf_exposure_intervals(int device, const double* counts, int64
     h_c.resize(P * T), h_f.resize(P * T), h_lo.resize(P), h_hi.resize(P), h_nt.resize(P), h_br.resize(P);
     DevBufs& d = *r.d;
     ProfileArgs a{};
-    a.prob_n = profile_upload(d, prob_n), a.prob_s = profile_upload(d, prob_s), a.end = profile_upload(d, end);
-    a.hhat = profile_upload(d, hhat), a.f1 = profile_upload(d, f1);
+    a.prob_n = upload(d, prob_n), a.prob_s = upload(d, prob_s), a.end = upload(d, end);
+    a.hhat = upload(d, hhat), a.f1 = upload(d, f1);
     a.trial_c = d.get<double>(P * T), a.trial_f = d.get<double>(P * T), a.trial_nit = d.get<int>(P * T), a.trial_conv = d.get<int>(P * T);
     a.lo = d.get<double>(P), a.hi = d.get<double>(P), a.n_trials = d.get<int>(P), a.bracketed = d.get<int>(P);
     if (!a.prob_n || !a.prob_s || !a.end || !a.hhat || !a.f1 || !a.trial_c || !a.trial_f || !a.trial_nit || !a.trial_conv || !a.lo || !a.hi ||
         !a.n_trials || !a.bracketed)
         return fail("hipMalloc or upload failed (%zu problems of %d trials, %d signatures)", P, T, K);
     a.P = (int64_t)P, a.T = T, a.n_bisections = J, a.max_expansions = E, a.delta = delta;
-    CK(r.launch(io, a));
-    HIPCK(hipMemcpyAsync(h_c.data(), a.trial_c, h_c.size() * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(h_f.data(), a.trial_f, h_f.size() * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(h_lo.data(), a.lo, P * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(h_hi.data(), a.hi, P * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(h_nt.data(), a.n_trials, P * sizeof(int), hipMemcpyDeviceToHost, d.stream));
-    HIPCK(hipMemcpyAsync(h_br.data(), a.bracketed, P * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+    CK(r.launch_profile_kernel(io, a));
+    CK(download(d, h_c.data(), a.trial_c, h_c.size()));
+    CK(download(d, h_f.data(), a.trial_f, h_f.size()));
+    CK(download(d, h_lo.data(), a.lo, P));
+    CK(download(d, h_hi.data(), a.hi, P));
+    CK(download(d, h_nt.data(), a.n_trials, P));
+    CK(download(d, h_br.data(), a.bracketed, P));
     HIPCK(hipStreamSynchronize(d.stream));
     for (size_t p = 0; p < P; ++p) {
         const size_t o = r.slot[prob_pair[p]];
@@ -1331,5 +1173,5 @@ extern "C" int salnmf_exposure_intervals(int device, const double* counts, int64
                 trace_profile[(2 * o + which) * T + i] = h_f[p * T + i] - f1[p];  // the kernel's own g, one rounded subtraction
             }
     }
-    return r.times(io, (int64_t)P);
+    return r.profile_times(io, (int64_t)P);
 }
