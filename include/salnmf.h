@@ -287,7 +287,11 @@ int salnmf_set_batched_sample_solves(salnmf_engine* e, int on);
  * on the device; W, the numerator's cross-workgroup sums and the W tail stay fp64; H is converted back at the end of every
  * salnmf_kl_step call, so every other entry point sees the usual fp64 state).  Unweighted steps only.  Tolerance: W, H
  * within 1e-5 rel-L2 of the fp64 step after 20 steps, within 1e-3 after 500 (the reference computes in fp64,
- * _utils_klnmf.py:7-9; the default SALNMF_PRECISION_F64 is the path all parity claims and benchmarks refer to). */
+ * _utils_klnmf.py:7-9; the default SALNMF_PRECISION_F64 is the path all parity claims and benchmarks refer to).
+ * Entry by entry, one step lies within (K + V + 8) 2^-24 (H) and 2 (K + 16 T + 8) 2^-24 (W) of the same step computed
+ * exactly on the fp32-rounded X, H and W (the tail multiplies the unrounded W); T = tiles of 16 samples per wave,
+ * ceil(ntiles / (4 grid)).  An entry below EPSILON comes back as EPSILON exactly; relative, because every sum has
+ * non-negative terms (tests/_f32_ref.py). */
 #define SALNMF_PRECISION_F64 0
 #define SALNMF_PRECISION_F32_FAST 1
 int salnmf_set_precision(salnmf_engine* e, int precision);
