@@ -793,6 +793,31 @@ int salnmf_exposure_intervals(int device, const double* counts, int64_t n_sample
                               int* n_trials, double* statistic, double* null_errors, double* exposures, double* errors,
                               double* trace_values, double* trace_profile, double* timings);
 
+/* ---- Which exposures trade against each other in a sample?  The information matrix of the sample's exposures at the fit, its
+ * inverse, and what the inverse says about confounding (csrc/salnmf_information.h).  counts, signatures
+ * as salnmf_refit_exposures (the counts clipped to SALNMF_EPSILON, the signature rows used as given); exposures  n_samples x
+ * n_signatures, finite and >= 0;  active  n_samples x n_signatures bytes, anything but 0 is "active".  Per sample:
+ *   p_v = max(sum_k W[k, v] h_k, SALNMF_EPSILON) over ALL k;  d_v = x_v / p_v^2 (information = 0, observed: the Hessian of the
+ *   sample's KL divergence) or 1 / p_v (information = 1, expected);  J[k, l] = sum_v W[k, v] W[l, v] d_v on the active k, l;
+ *   C = D^-1/2 J D^-1/2 with D = diag(J);  C = L L^T in the natural order of k without pivoting;  min_pivot_value is the
+ *   smallest L[k, k]^2, and the sample is SINGULAR at the first squared pivot <= min_pivot (min_pivot_value is then that pivot).
+ * Outputs, n_samples x n_signatures: standard_errors = sqrt((C^-1)_kk / J_kk);  inflation = (C^-1)_kk;  information_diag = J_kk;
+ * max_abs_correlation and most_confounded: the largest |corr_kl| over the active l != k and its index, the smallest on a tie,
+ * corr_kl = (C^-1)_kl / sqrt((C^-1)_kk (C^-1)_ll) -- NaN and -1 where k is inactive, the sample is singular, or k is the only
+ * active signature.  The three others are NaN where k is inactive or the sample is singular.  n_samples: min_pivot_value (NaN
+ * without an active signature), singular (1 / 0), n_active.  correlation  NULL, or n_samples x n_signatures x n_signatures:
+ * corr with a unit diagonal on the active set, NaN elsewhere, symmetric bit for bit; it is produced in chunks of samples whose
+ * device buffer stays within chunk_bytes (0 or less: 256 MiB).  A sample's results depend on that sample alone.  timings: NULL,
+ * or 2 doubles -- milliseconds by device events of the kernel launches, and the number of launches.
+ * Refused on the host before any launch, status 1 and salnmf_last_error: a null argument other than correlation and timings;
+ * n_samples outside [1, 2^31), n_features or n_signatures outside [1, 96]; counts, signatures or exposures that are not finite or
+ * are negative, a signature without a positive sum; information not 0 or 1; min_pivot not finite or outside (0, 1). */
+int salnmf_exposure_covariance(int device, const double* counts, int64_t n_samples, int n_features, const double* signatures,
+                               int n_signatures, const double* exposures, const unsigned char* active, int information,
+                               double min_pivot, int64_t chunk_bytes, double* standard_errors, double* inflation,
+                               double* information_diag, double* max_abs_correlation, int* most_confounded,
+                               double* min_pivot_value, int* singular, int* n_active, double* correlation, double* timings);
+
 #ifdef __cplusplus
 }
 #endif

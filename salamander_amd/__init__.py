@@ -10,6 +10,7 @@ from . import models
 from ._lib import EngineUnavailable
 from .anndata_compat import AnnData, MuData
 from .assign import AssignResult, assign_signatures
+from .covariance import CovarianceResult, exposure_covariance
 from .engine import Engine
 from .gof import GofResult, draw_model_counts, goodness_of_fit
 from .intervals import IntervalResult, ProfileResult, exposure_intervals, profile_likelihood
@@ -23,4 +24,5 @@ from .stability import signature_stability
 __version__ = "0.1.0"
 __all__ = ["models", "Engine", "AnnData", "MuData", "EngineUnavailable", "resample_counts", "signature_stability", "refit_exposures", "RefitResult", "assign_signatures",
            "AssignResult", "split_counts", "goodness_of_fit", "draw_model_counts", "GofResult", "signature_presence_test",
-           "PresenceResult", "signature_power", "PowerResult", "profile_likelihood", "ProfileResult", "exposure_intervals", "IntervalResult"]
+           "PresenceResult", "signature_power", "PowerResult", "profile_likelihood", "ProfileResult", "exposure_intervals", "IntervalResult",
+           "exposure_covariance", "CovarianceResult"]

@@ -155,6 +155,9 @@ SIGNATURES = {
                                           c_double, POINTER(c_uint8), _D, _D, _I, _I, _D, _D, _D, _D]),
     "salnmf_exposure_intervals": (c_int, [c_int, _D, c_int64, c_int, _D, c_int, _I, c_int, POINTER(c_uint8), c_double, c_int, c_int, c_int, c_int, c_int,
                                           c_double, POINTER(c_uint8), _D, _D, _D, POINTER(c_uint8), _I, _D, _D, _D, _D, _D, _D, _D]),
+    # the information matrix of a sample's exposures, its inverse and the confounding it shows: salamander_amd/covariance.py
+    "salnmf_exposure_covariance": (c_int, [c_int, _D, c_int64, c_int, _D, c_int, _D, POINTER(c_uint8), c_int, c_double, c_int64,
+                                           _D, _D, _D, _D, _I, _D, _I, _I, _D, _D]),
 }
 
 OBJECTIVE_SLOTS = 256  # SALNMF_OBJECTIVE_SLOTS

@@ -8,12 +8,14 @@
 // and of the profile likelihood of one exposure and its interval (salnmf_profile_likelihood, salnmf_exposure_intervals;
 // salnmf_profile.h: profile_kernel), DESIGN.md section 19.
 // The four tile-solve kernels share the solve_* pieces of salnmf_refit.h; the drivers below share one kit:
-// launch_tiles, Spans, chunk_rows, fill_reduce, upload / download, and for the pair calls pair_observed and pair_draw_solve.
+// launch_tiles, fill_reduce, from salnmf_host_kit.h Spans, chunk_rows and upload / download, and for the pair calls pair_observed and
+// pair_draw_solve.
 #define SALNMF_TEMPLATES_ONLY 1
 #define SALNMF_REFIT_KERNELS 1
 #include "../../include/salnmf.h"
 #include "salnmf_kernels.h"
 #include "salnmf_device.h"
+#include "salnmf_host_kit.h"
 #include "salnmf_refit.h"
 #include "salnmf_assign.h"
 #include "salnmf_gof.h"
@@ -118,7 +120,8 @@ int refit_prepare(int device, const double* counts, int64_t N, int V, const doub
     return 0;
 }
 
-// ---- the host kit of the family: one tile launcher, one span timer, one chunk rule, one reduce fill.
+// ---- the host kit of the family: one tile launcher and one reduce fill here; the span timer, the chunk
+// rule and the copies in salnmf_host_kit.h.
 
 // What every tile-solve kernel's launch does: one workgroup per CU (the kernels' registers leave room for one wave per SIMD; waves
 // fetch tiles until the list is empty), the list's head reset, and the instantiation for (K + 15) / 16 signature tiles, which
@@ -165,79 +168,12 @@ int launch_profile(const ProfileArgs& a, int cus, hipStream_t stream) {
                         [&](auto kt, dim3 grid) { hipLaunchKernelGGL(profile_kernel<decltype(kt)::value>, grid, dim3(BLOCK), 0, stream, a); });
 }
 
-// Device-event spans around groups of launches on d's stream, summed per group; nothing is recorded unless `on`.
-struct Spans {
-    static constexpr int GROUPS = 7;  // the most any driver has (the power analysis)
-    DevBufs* d = nullptr;
-    bool on = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> spans[GROUPS];
-
-    void start(DevBufs& bufs, bool timing) { d = &bufs, on = timing; }
-    template <typename F>
-    int timed(int which, F&& body) {
-        if (which < 0 || which >= GROUPS) return fail("span group %d out of range", which);
-        hipEvent_t e0 = on ? d->mark() : nullptr;
-        CK(body());
-        hipEvent_t e1 = on ? d->mark() : nullptr;
-        if (on && (!e0 || !e1)) return fail("event record failed");
-        if (on) spans[which].emplace_back(e0, e1);
-        return 0;
-    }
-    // (after the stream has been waited for)
-    int total_ms(int which, double* out) {
-        double total = 0.0;
-        for (const auto& pr : spans[which]) {
-            float ms = 0.f;
-            HIPCK(hipEventElapsedTime(&ms, pr.first, pr.second));
-            total += (double)ms;
-        }
-        *out = total;
-        return 0;
-    }
-    // groups 0 .. count - 1 into out[0 .. count - 1]; nothing when timing is off
-    int totals(int count, double* out) {
-        for (int i = 0; on && i < count; ++i) CK(total_ms(i, out + i));
-        return 0;
-    }
-};
-
-// Rows of a chunk buffer: as many of `rows` as budget_bytes allows (0 or less: 256 MiB), at least one
-int64_t chunk_rows(int64_t budget_bytes, size_t row_bytes, int64_t rows) {
-    const int64_t budget = budget_bytes > 0 ? budget_bytes : (int64_t)256 << 20;
-    return std::max<int64_t>(1, std::min<int64_t>(rows, budget / (int64_t)row_bytes));
-}
-
 // The resamples' reduction over H [R][N][K] (red.index is refit_prepare's)
 void fill_reduce(RefitReduceArgs& red, const double* H, double* quant, double* mean, int64_t N, int K, int R, int Q) {
     red.H = H, red.quant = quant, red.mean = mean;
     red.N = N, red.K = K, red.R = R, red.Q = Q;
     red.R2 = 1;
     while (red.R2 < R) red.R2 <<= 1;
-}
-
-// n entries of `host` in a new buffer of d, copied on its stream: the device pointer, or null (the allocation or the copy
-// failed).  The host side lives until d's destructor has waited for the stream: it is declared before d.
-template <typename T>
-T* upload(DevBufs& d, const T* host, size_t n) {
-    T* dev = d.get<T>(n);
-    if (dev && hipMemcpyAsync(dev, host, n * sizeof(T), hipMemcpyHostToDevice, d.stream) != hipSuccess) return nullptr;
-    return dev;
-}
-template <typename T>
-T* upload(DevBufs& d, const std::vector<T>& host) {
-    return upload(d, host.data(), host.size());
-}
-
-// n entries of the device buffer `src` to `dst` on d's stream (not waited for)
-template <typename D, typename S>
-int download(DevBufs& d, D* dst, const S* src, size_t n) {
-    static_assert(sizeof(D) == sizeof(S), "download: element sizes differ");
-    HIPCK(hipMemcpyAsync(dst, src, n * sizeof(S), hipMemcpyDeviceToHost, d.stream));
-    return 0;
-}
-template <typename T, typename S>
-int download(DevBufs& d, std::vector<T>& dst, const S* src) {
-    return download(d, dst.data(), src, dst.size());
 }
 
 }  // namespace

@@ -13,6 +13,7 @@ c=salamander_amd/csrc
 ( /opt/rocm/bin/hipcc $flags -c $c/salnmf_small.hip -o $obj/small.o ) &
 ( /opt/rocm/bin/hipcc $flags -c $c/salnmf_batch.hip -o $obj/batch.o ) &
 ( /opt/rocm/bin/hipcc $flags -c $c/salnmf_refit.hip -o $obj/refit.o ) &
+( /opt/rocm/bin/hipcc $flags -c $c/salnmf_information.hip -o $obj/information.o ) &
 wait
 for i in 0 1 2 3 4 5; do ( /opt/rocm/bin/hipcc $flags -DSALNMF_GEOM_SET=$i -c $c/salnmf_fused_inst.hip -o $obj/fused_inst_$i.o ) & done
 wait
