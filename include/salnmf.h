@@ -818,6 +818,43 @@ int salnmf_exposure_covariance(int device, const double* counts, int64_t n_sampl
                                double* information_diag, double* max_abs_correlation, int* most_confounded,
                                double* min_pivot_value, int* singular, int* n_active, double* correlation, double* timings);
 
+/* ---- Have the exposure SHARES changed between two samples of one patient?  A likelihood-ratio test of "same shares, free
+ * totals" against "own exposures" per pair of rows, with a parametric-bootstrap null (csrc/salnmf_change.h, DESIGN.md section
+ * 21).  Row n of counts_a and row n of counts_b form pair n: both n_samples x n_features (the second shape is passed and must
+ * agree).  signatures, candidates, the iteration arguments, max_iterations % conv_test_freq == 0, n_draws, seed and chunk_bytes as
+ * salnmf_signature_presence; candidates holds one set C_n per pair, for both samples and for the pooled fit.  Contract, for pair n
+ * with clipped rows x_a, x_b (each max(row, SALNMF_EPSILON)):
+ *   solve a, solve b and the pooled solve are salnmf_signature_presence's SOLVE ON A SET C_n of x_a, of x_b and of the row
+ *   x_p[v] = x_a[v] + x_b[v], each from a cold start -- bit for bit the exposures, error, iteration count and convergence flag
+ *   of salnmf_assign_signatures_ex with candidates = required = C_n on that row: (h_a, f_a), (h_b, f_b), (h_0, f_p);
+ *   with t the rows' sums, c_a = t_a / (t_a + t_b), c_b = t_b / (t_a + t_b) and P_0 = h_0 W as the pooled solve holds it at its
+ *   stopping test: g_a = KL(x_a || c_a P_0), g_b = KL(x_b || c_b P_0), the refit's objective term by term;
+ *   statistic[n] = (g_a - f_a) + (g_b - f_b), half the likelihood-ratio statistic;
+ *   the pair is UNTESTED if C_n has fewer than two members or either row's integer total is 0: tested[n] = 0, it draws nothing
+ *   and costs no solve;
+ *   null draw b of the pair is two model draws (salnmf_draw_model_counts' steps) from the exposures h_0, one of sum_v counts_a[n, v]
+ *   trials and one of sum_v counts_b[n, v], with the Philox counter (q, 0x43480000 + side, n, b), side 0 for a and 1 for b: a
+ *   stream family of its own ("CH" in the upper half of the second word), so the draws of a pair depend on (seed, n, side, b) and
+ *   on h_0 only;
+ *   every draw pair goes through the same three solves and the same two divergences: null_statistics[b, n];
+ *   reduction as salnmf_signature_presence: n_exceed[n] counts null_statistics[b, n] >= statistic[n] (false for a NaN on either
+ *   side), null_mean[n] is their sum from 0.0 in ascending b, divided by n_draws.  The p-value is (1 + n_exceed) / (n_draws + 1).
+ * Outputs: tested (1 / 0), statistic, n_exceed, null_mean  n_samples;  exposures_a (h_a), exposures_b (h_b), pooled_exposures (h_0)
+ * n_samples x n_signatures;  errors  n_samples x 3 (f_a, f_b, f_p);  null_errors  n_samples x 2 (g_a, g_b);  n_iterations, converged
+ * n_samples x 3 (a, b, pooled);  null_statistics  n_draws x n_samples;  null_n_iterations  n_draws x n_samples x 3;  draws  NULL, or
+ * n_draws x n_samples x 2 x n_features, plain counts.  Entries of an untested pair: NaN in the doubles (0 in draws), 0 in the
+ * integers.  timings: NULL, or 4 doubles -- milliseconds by device events of the draw launches, the solve launches and the
+ * reduction, and the number of chunks.
+ * Refused on the host before any launch, status 1 and salnmf_last_error: a null argument other than candidates, draws and
+ * timings; shapes that differ; what salnmf_signature_presence refuses of these arguments, for either count matrix. */
+int salnmf_exposure_change(int device, const double* counts_a, int64_t n_samples, int n_features, const double* counts_b,
+                           int64_t n_samples_b, int n_features_b, const double* signatures, int n_signatures,
+                           const uint8_t* candidates, int n_draws, uint64_t seed, int min_iterations, int max_iterations,
+                           int conv_test_freq, double tol, int64_t chunk_bytes, uint8_t* tested, double* statistic, int* n_exceed,
+                           double* null_mean, double* exposures_a, double* exposures_b, double* pooled_exposures, double* errors,
+                           double* null_errors, int* n_iterations, int* converged, double* null_statistics,
+                           int* null_n_iterations, double* draws, double* timings);
+
 #ifdef __cplusplus
 }
 #endif

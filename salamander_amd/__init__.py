@@ -10,6 +10,7 @@ from . import models
 from ._lib import EngineUnavailable
 from .anndata_compat import AnnData, MuData
 from .assign import AssignResult, assign_signatures
+from .change import ChangeResult, exposure_change_test
 from .covariance import CovarianceResult, exposure_covariance
 from .engine import Engine
 from .gof import GofResult, draw_model_counts, goodness_of_fit
@@ -25,4 +26,4 @@ __version__ = "0.1.0"
 __all__ = ["models", "Engine", "AnnData", "MuData", "EngineUnavailable", "resample_counts", "signature_stability", "refit_exposures", "RefitResult", "assign_signatures",
            "AssignResult", "split_counts", "goodness_of_fit", "draw_model_counts", "GofResult", "signature_presence_test",
            "PresenceResult", "signature_power", "PowerResult", "profile_likelihood", "ProfileResult", "exposure_intervals", "IntervalResult",
-           "exposure_covariance", "CovarianceResult"]
+           "exposure_covariance", "CovarianceResult", "exposure_change_test", "ChangeResult"]

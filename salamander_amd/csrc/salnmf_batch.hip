@@ -14,6 +14,7 @@
 #define SALNMF_GOF_KERNELS 1
 #include "salnmf_gof.h"
 #include "salnmf_presence.h"
+#include "salnmf_change.h"
 #include "salnmf_power.h"
 #include "salnmf_stability.h"
 
@@ -328,6 +329,17 @@ void salnmf::presence_launch_draw(const double* H0, const double* W, const doubl
         const PresenceDrawArgs a{H0, W, X, pair_n, pair_s, out + (size_t)done * NP * V, NP, V, K, (uint32_t)seed, (uint32_t)(seed >> 32), floor,
                                  (uint32_t)(first + done)};
         hipLaunchKernelGGL(presence_draw_kernel, dim3((unsigned)NP, (unsigned)now), dim3(RESAMPLE_BLOCK), 0, stream, a);
+    }
+}
+
+// the change test's draw (salnmf_change.h): the same body, one workgroup per (pair, side, draw)
+void salnmf::change_launch_draw(const double* H0, const double* W, const double* Xa, const double* Xb, const int* pair_n, double* out, int64_t NP, int V,
+                                int K, uint64_t seed, double floor, int first, int count, hipStream_t stream) {
+    for (int done = 0; done < count; done += GOF_GRID_Y) {
+        const int now = std::min(GOF_GRID_Y, count - done);
+        const ChangeDrawArgs a{H0, W, Xa, Xb, pair_n, out + (size_t)done * NP * 2 * V, NP, V, K, (uint32_t)seed, (uint32_t)(seed >> 32), floor,
+                               (uint32_t)(first + done)};
+        hipLaunchKernelGGL(change_draw_kernel, dim3((unsigned)(2 * NP), (unsigned)now), dim3(RESAMPLE_BLOCK), 0, stream, a);
     }
 }
 
