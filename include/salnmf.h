@@ -855,6 +855,43 @@ int salnmf_exposure_change(int device, const double* counts_a, int64_t n_samples
                            double* null_errors, int* n_iterations, int* converged, double* null_statistics,
                            int* null_n_iterations, double* draws, double* timings);
 
+/* ---- WHICH signature's share has changed between the two samples of a pair?  A likelihood-ratio test of "signature s has the
+ * same share in both samples, everything else free" against "own exposures", per (pair, tested signature), with a
+ * parametric-bootstrap null (csrc/salnmf_sigchange.h).  counts_a, counts_b, signatures, candidates, the
+ * iteration arguments, n_draws, seed and chunk_bytes as salnmf_exposure_change; test as salnmf_signature_presence (n_test distinct
+ * indices).  Contract, for pair n with clipped rows x_a, x_b, candidate set C_n and s = test[j]:
+ *   t_a, t_b are the clipped rows' sums, c_a = t_a / (t_a + t_b), c_b = t_b / (t_a + t_b); the share of s in a sample is h_s / t;
+ *   solves a and b are salnmf_exposure_change's: (h_a, f_a), (h_b, f_b);
+ *   the TIED solve runs both samples side by side from the cold start h_k = t_side / |C_n|: every entry but s takes its own
+ *   sample's update factor, entry s takes F = c_a u_as + c_b u_bs, evaluated as (u_as + u_bs) / 2 + ((c_a - c_b) / 2) (u_as - u_bs) with every operation
+ *   rounded on its own (so that equal factors give that factor, and the two samples can be exchanged), in both samples; the
+ *   EPSILON clip is per sample; the objective f_a0 + f_b0 (one rounded sum) is tested at iteration 0 and at every multiple of
+ *   conv_test_freq by the family's stop rule, and both samples stop together: (h_a0, f_a0), (h_b0, f_b0);
+ *   statistic[n, j] = (f_a0 - f_a) + (f_b0 - f_b), half the likelihood-ratio statistic with one constrained parameter; exchanging
+ *   counts_a and counts_b exchanges the sides' results and leaves its bits;
+ *   the problem is UNTESTED if s is not in C_n, C_n has fewer than two members or either row's integer total is 0: tested[n, j] = 0,
+ *   it draws nothing and costs no solve;
+ *   null draw b of the problem is two model draws (salnmf_draw_model_counts' steps), side a from the exposures h_a0 with
+ *   sum_v counts_a[n, v] trials and side b from h_b0 with sum_v counts_b[n, v], under the Philox counter
+ *   (q, 0x53430000 + 2 s + side, n, b): a stream family of its own ("SC" in the upper half of the second word);
+ *   every draw pair goes through the same three solves: null_statistics[b, n, j]; reduction as salnmf_signature_presence.
+ * Outputs: tested (1 / 0), statistic, n_exceed, null_mean  n_samples x n_test;  exposures_a (h_a), exposures_b (h_b)  n_samples x
+ * n_signatures (NaN rows where no problem of the pair is tested);  tied_exposures_a (h_a0), tied_exposures_b (h_b0)  n_samples x n_test
+ * x n_signatures;  errors  n_samples x n_test x 4 (f_a, f_b, f_a0, f_b0);  n_iterations, converged  n_samples x n_test x 3 (a, b,
+ * tied);  null_statistics  n_draws x n_samples x n_test;  null_n_iterations  n_draws x n_samples x n_test x 3;  draws  NULL, or n_draws
+ * x n_samples x n_test x 2 x n_features, plain counts.  Entries of an untested problem: NaN in the doubles (0 in draws), 0 in the
+ * integers.  timings: NULL, or 4 doubles -- milliseconds by device events of the draw launches, the solve launches and the
+ * reduction, and the number of chunks.
+ * Refused on the host before any launch, status 1 and salnmf_last_error: a null argument other than candidates, draws and
+ * timings; shapes that differ; what salnmf_exposure_change and salnmf_signature_presence refuse of these arguments. */
+int salnmf_signature_change(int device, const double* counts_a, int64_t n_samples, int n_features, const double* counts_b,
+                            int64_t n_samples_b, int n_features_b, const double* signatures, int n_signatures, const int* test,
+                            int n_test, const uint8_t* candidates, int n_draws, uint64_t seed, int min_iterations,
+                            int max_iterations, int conv_test_freq, double tol, int64_t chunk_bytes, uint8_t* tested,
+                            double* statistic, int* n_exceed, double* null_mean, double* exposures_a, double* exposures_b,
+                            double* tied_exposures_a, double* tied_exposures_b, double* errors, int* n_iterations, int* converged,
+                            double* null_statistics, int* null_n_iterations, double* draws, double* timings);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,7 @@ from .power import PowerResult, signature_power
 from .presence import PresenceResult, signature_presence_test
 from .refit import RefitResult, refit_exposures
 from .resample import resample_counts
+from .sigchange import SignatureChangeResult, signature_change_test
 from .split import split_counts
 from .stability import signature_stability
 
@@ -26,4 +27,5 @@ __version__ = "0.1.0"
 __all__ = ["models", "Engine", "AnnData", "MuData", "EngineUnavailable", "resample_counts", "signature_stability", "refit_exposures", "RefitResult", "assign_signatures",
            "AssignResult", "split_counts", "goodness_of_fit", "draw_model_counts", "GofResult", "signature_presence_test",
            "PresenceResult", "signature_power", "PowerResult", "profile_likelihood", "ProfileResult", "exposure_intervals", "IntervalResult",
-           "exposure_covariance", "CovarianceResult", "exposure_change_test", "ChangeResult"]
+           "exposure_covariance", "CovarianceResult", "exposure_change_test", "ChangeResult", "signature_change_test",
+           "SignatureChangeResult"]

@@ -161,6 +161,9 @@ SIGNATURES = {
     # changed exposure shares between two samples, per pair of rows: salamander_amd/change.py
     "salnmf_exposure_change": (c_int, [c_int, _D, c_int64, c_int, _D, c_int64, c_int, _D, c_int, POINTER(c_uint8), c_int, c_uint64, c_int, c_int, c_int,
                                        c_double, c_int64, POINTER(c_uint8), _D, _I, _D, _D, _D, _D, _D, _D, _I, _I, _D, _I, _D, _D]),
+    # which signature's share has changed between two samples, per pair of rows and tested signature: salamander_amd/sigchange.py
+    "salnmf_signature_change": (c_int, [c_int, _D, c_int64, c_int, _D, c_int64, c_int, _D, c_int, _I, c_int, POINTER(c_uint8), c_int, c_uint64, c_int,
+                                        c_int, c_int, c_double, c_int64, POINTER(c_uint8), _D, _I, _D, _D, _D, _D, _D, _D, _I, _I, _D, _I, _D, _D]),
 }
 
 OBJECTIVE_SLOTS = 256  # SALNMF_OBJECTIVE_SLOTS

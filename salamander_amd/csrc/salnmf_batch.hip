@@ -15,6 +15,7 @@
 #include "salnmf_gof.h"
 #include "salnmf_presence.h"
 #include "salnmf_change.h"
+#include "salnmf_sigchange.h"
 #include "salnmf_power.h"
 #include "salnmf_stability.h"
 
@@ -340,6 +341,18 @@ void salnmf::change_launch_draw(const double* H0, const double* W, const double*
         const ChangeDrawArgs a{H0, W, Xa, Xb, pair_n, out + (size_t)done * NP * 2 * V, NP, V, K, (uint32_t)seed, (uint32_t)(seed >> 32), floor,
                                (uint32_t)(first + done)};
         hipLaunchKernelGGL(change_draw_kernel, dim3((unsigned)(2 * NP), (unsigned)now), dim3(RESAMPLE_BLOCK), 0, stream, a);
+    }
+}
+
+// the per-signature change test's draw (salnmf_sigchange.h): the same body, one workgroup per (problem, side, draw)
+void salnmf::sigchange_launch_draw(const double* Ha0, const double* Hb0, const double* W, const double* Xa, const double* Xb, const int* pair_n,
+                                   const int* pair_s, double* out, int64_t NP, int V, int K, uint64_t seed, double floor, int first, int count,
+                                   hipStream_t stream) {
+    for (int done = 0; done < count; done += GOF_GRID_Y) {
+        const int now = std::min(GOF_GRID_Y, count - done);
+        const SigChangeDrawArgs a{Ha0, Hb0, W, Xa, Xb, pair_n, pair_s, out + (size_t)done * NP * 2 * V, NP, V, K, (uint32_t)seed, (uint32_t)(seed >> 32),
+                                  floor, (uint32_t)(first + done)};
+        hipLaunchKernelGGL(sigchange_draw_kernel, dim3((unsigned)(2 * NP), (unsigned)now), dim3(RESAMPLE_BLOCK), 0, stream, a);
     }
 }
 

@@ -7,8 +7,9 @@
 // and of that test's power analysis (salnmf_signature_power; salnmf_power.h: its three kernels in salnmf_batch.hip), DESIGN.md section 18;
 // and of the profile likelihood of one exposure and its interval (salnmf_profile_likelihood, salnmf_exposure_intervals;
 // salnmf_profile.h: profile_kernel); and of the test of changed exposure shares between two samples
-// (salnmf_exposure_change; salnmf_change.h: change_kernel here, change_draw_kernel in salnmf_batch.hip), DESIGN.md section 21.
-// The five tile-solve kernels share the solve_* pieces of salnmf_refit.h; the drivers below share one kit:
+// (salnmf_exposure_change; salnmf_change.h: change_kernel here, change_draw_kernel in salnmf_batch.hip); and of
+// the per-signature test of a changed share (salnmf_signature_change; salnmf_sigchange.h: sigchange_kernel here, sigchange_draw_kernel in
+// salnmf_batch.hip), DESIGN.md section 22.  The six tile-solve kernels share the solve_* pieces of salnmf_refit.h; the drivers below share one kit:
 // launch_tiles, fill_reduce, from salnmf_host_kit.h Spans, chunk_rows and upload / download, and for the pair calls pair_observed and
 // pair_draw_solve.
 #define SALNMF_TEMPLATES_ONLY 1
@@ -22,6 +23,7 @@
 #include "salnmf_gof.h"
 #include "salnmf_presence.h"
 #include "salnmf_change.h"
+#include "salnmf_sigchange.h"
 #include "salnmf_power.h"
 #include "salnmf_profile.h"
 
@@ -1278,6 +1280,192 @@ extern "C" int salnmf_exposure_change(int device, const double* counts_a, int64_
                 for (int i = 0; i < 2 * V; ++i) {
                     const double c = h_draws[(b * NP + j) * 2 * V + i];
                     draws[(b * N + o) * 2 * V + i] = c < 1.0 ? 0.0 : c;
+                }
+        }
+    }
+    CK(sp.totals(3, timings));
+    if (timings) timings[3] = (double)n_chunks;
+    return 0;
+}
+
+// ---- which signature's share has changed between two samples?  Two free solves and one tied solve per (pair, tested signature) and
+// per null draw, a problem in two adjacent lane columns (salnmf_sigchange.h).  The driver is the change test's
+// on the presence test's pair list: the observed launch, per chunk a draw and a solve launch, gof_reduce_kernel over the problems,
+// the downloads -- one stream, nothing waited for in between.
+
+namespace {
+
+int launch_sigchange(const SigChangeArgs& a, int cus, hipStream_t stream) {
+    // the tile list is of lane columns, two per problem
+    return launch_tiles("signature change", 2 * a.P, a.K, a.next_tile, cus, stream,
+                        [&](auto kt, dim3 grid) { hipLaunchKernelGGL(sigchange_kernel<decltype(kt)::value>, grid, dim3(BLOCK), 0, stream, a); });
+}
+
+}  // namespace
+
+extern "C" int salnmf_signature_change(int device, const double* counts_a, int64_t n_samples, int n_features, const double* counts_b,
+                                       int64_t n_samples_b, int n_features_b, const double* signatures, int n_signatures, const int* test, int n_test,
+                                       const uint8_t* candidates, int n_draws, uint64_t seed, int min_iterations, int max_iterations,
+                                       int conv_test_freq, double tol, int64_t chunk_bytes, uint8_t* tested, double* statistic, int* n_exceed,
+                                       double* null_mean, double* exposures_a, double* exposures_b, double* tied_exposures_a, double* tied_exposures_b,
+                                       double* errors, int* n_iterations, int* converged, double* null_statistics, int* null_n_iterations,
+                                       double* draws, double* timings) {
+    const int64_t N = n_samples;
+    const int V = n_features, K = n_signatures, B = n_draws, S = n_test;
+    if (!counts_a || !counts_b || !signatures || !test || !tested || !statistic || !n_exceed || !null_mean || !exposures_a || !exposures_b ||
+        !tied_exposures_a || !tied_exposures_b || !errors || !n_iterations || !converged || !null_statistics || !null_n_iterations)
+        return fail("null argument");
+    if (n_samples_b != N || n_features_b != V)
+        return fail("row n of counts_a and row n of counts_b form pair n: the shapes must agree, got %lld x %d and %lld x %d", (long long)N, V,
+                    (long long)n_samples_b, n_features_b);
+    CK(gof_check_draws(B));
+    if (conv_test_freq >= 1 && max_iterations >= 0 && max_iterations % conv_test_freq != 0)
+        return fail("max_iterations must be a multiple of conv_test_freq, got %d and %d", max_iterations, conv_test_freq);
+    // the host ends of the asynchronous copies live until d's destructor has waited for the stream: d is declared after them
+    RefitInputs in, in_b;
+    CK(refit_prepare(device, counts_a, N, V, signatures, K, 0, 0, nullptr, min_iterations, max_iterations, conv_test_freq, tol, true, in,
+                     AssignSets{candidates, nullptr, 0}));
+    CK(refit_prepare(device, counts_b, N, V, signatures, K, 0, 0, nullptr, min_iterations, max_iterations, conv_test_freq, tol, true, in_b));
+    CK(presence_check_test(test, S, K));
+    CK(refit_check_counts(counts_a, N, V, in.icounts));  // integer counts, row totals below 2^32
+    CK(refit_check_counts(counts_b, N, V, in_b.icounts));
+    const int cus = in.cus;
+
+    // the tested problems: s a candidate and not the only one (the presence test's list), and a positive total on either side
+    std::vector<int> pair_n, pair_s;
+    std::vector<size_t> slot;
+    presence_list_pairs(in, N, K, test, S, candidates != nullptr, tested, pair_n, pair_s, slot);
+    {
+        size_t kept = 0;
+        for (size_t j = 0; j < pair_n.size(); ++j) {
+            const size_t n = (size_t)pair_n[j];
+            uint64_t total_a = 0, total_b = 0;
+            for (int v = 0; v < V; ++v) total_a += in.icounts[n * V + v], total_b += in_b.icounts[n * V + v];
+            if (total_a > 0 && total_b > 0)
+                pair_n[kept] = pair_n[j], pair_s[kept] = pair_s[j], slot[kept] = slot[j], ++kept;
+            else
+                tested[slot[j]] = 0;
+        }
+        pair_n.resize(kept), pair_s.resize(kept), slot.resize(kept);
+    }
+    const size_t NP = pair_n.size();
+    if (NP > 0x3fffffff) return fail("%zu tested problems: at most 2^30 - 1", NP);  // (the draw's grid: two workgroups per problem)
+    const double nan = std::nan("");
+    const size_t NS = (size_t)N * S, NK = (size_t)N * K, NB = NS * B;
+    std::fill(statistic, statistic + NS, nan);
+    std::fill(null_mean, null_mean + NS, nan);
+    std::fill(n_exceed, n_exceed + NS, 0);
+    std::fill(exposures_a, exposures_a + NK, nan);
+    std::fill(exposures_b, exposures_b + NK, nan);
+    std::fill(tied_exposures_a, tied_exposures_a + NS * K, nan);
+    std::fill(tied_exposures_b, tied_exposures_b + NS * K, nan);
+    std::fill(errors, errors + 4 * NS, nan);
+    std::fill(n_iterations, n_iterations + 3 * NS, 0);
+    std::fill(converged, converged + 3 * NS, 0);
+    std::fill(null_statistics, null_statistics + NB, nan);
+    std::fill(null_n_iterations, null_n_iterations + 3 * NB, 0);
+    if (draws) std::fill(draws, draws + 2 * NB * V, 0.0);
+    if (timings) timings[0] = timings[1] = timings[2] = timings[3] = 0.0;
+    if (NP == 0) return 0;
+
+    // draws per chunk: the [chunk][problems][2][V] buffer stays within chunk_bytes (at least one draw)
+    const size_t PV2 = NP * 2 * V, PK = NP * K, PB = NP * B;
+    const int chunk = (int)chunk_rows(chunk_bytes, sizeof(double) * PV2, B);
+    std::vector<double> h_stat(NP), h_f(4 * NP), h_Ha(PK), h_Hb(PK), h_Ha0(PK), h_Hb0(PK), h_mean(NP), h_stat_b(PB), h_draws(draws ? PB * 2 * V : 0);
+    std::vector<int> h_nit(3 * NP), h_conv(3 * NP), h_exceed(NP), h_nit_b(3 * PB);
+
+    DevBufs d;
+    CK(d.own_stream());
+    double* dW = upload(d, signatures, (size_t)K * V);
+    double* dXa = upload(d, in.x);
+    double* dXb = upload(d, in_b.x);
+    int* dpn = upload(d, pair_n);
+    int* dps = upload(d, pair_s);
+    uint32_t* dcand = candidates ? upload(d, in.cand) : nullptr;
+    double* dstat = d.get<double>(NP);
+    double* df = d.get<double>(4 * NP);
+    int* dnit = d.get<int>(3 * NP);
+    int* dconv = d.get<int>(3 * NP);
+    double* dHa = d.get<double>(PK);
+    double* dHb = d.get<double>(PK);
+    double* dHa0 = d.get<double>(PK);
+    double* dHb0 = d.get<double>(PK);
+    unsigned* dnext = d.get<unsigned>(1);
+    double* dXd = d.get<double>((size_t)chunk * PV2);
+    double* dstat_b = d.get<double>(PB);
+    int* dnit_b = d.get<int>(3 * PB);
+    int* dexceed = d.get<int>(NP);
+    double* dmean = d.get<double>(NP);
+    if (!dW || !dXa || !dXb || !dpn || !dps || (candidates && !dcand) || !dstat || !df || !dnit || !dconv || !dHa || !dHb || !dHa0 || !dHb0 || !dnext ||
+        !dXd || !dstat_b || !dnit_b || !dexceed || !dmean)
+        return fail("hipMalloc or upload failed (%d draws of %zu problems x 2 x %d, %d signatures)", B, NP, V, K);
+
+    Spans sp;  // draw, solve, reduce
+    sp.start(d, timings != nullptr);
+    const SigChangeArgs a{dXa, dXb, dW, dpn, dps, dcand, dstat, dnit, df, dconv, dHa, dHb, dHa0, dHb0, dnext, (int64_t)NP, (int64_t)NP, (int64_t)V, V, K, 1,
+                          min_iterations, max_iterations, conv_test_freq, tol};
+    CK(sp.timed(1, [&] { return launch_sigchange(a, cus, d.stream); }));
+    int n_chunks = 0;
+    for (int first = 0; first < B; first += chunk, ++n_chunks) {
+        const int count = std::min(chunk, B - first);
+        // from the device-resident exposures of the observed tied fits; a side's trial count is read off its clipped counts
+        CK(sp.timed(0, [&]() -> int {
+            sigchange_launch_draw(dHa0, dHb0, dW, dXa, dXb, dpn, dps, dXd, (int64_t)NP, V, K, seed, SALNMF_EPSILON, first, count, d.stream);
+            HIPCK(hipGetLastError());
+            return 0;
+        }));
+        if (draws) CK(download(d, h_draws.data() + (size_t)first * PV2, dXd, (size_t)count * PV2));
+        SigChangeArgs c = a;
+        c.Xa = dXd, c.Xb = dXd + V, c.stride = 2 * (int64_t)V, c.by_sample = 0;
+        c.P = (int64_t)count * (int64_t)NP;
+        c.stat = dstat_b + (size_t)first * NP;
+        c.nit = dnit_b + 3 * (size_t)first * NP;
+        c.f = nullptr, c.conv = nullptr, c.Ha = nullptr, c.Hb = nullptr, c.Ha0 = nullptr, c.Hb0 = nullptr;
+        CK(sp.timed(1, [&] { return launch_sigchange(c, cus, d.stream); }));
+    }
+    // gof_reduce_kernel over the problems: n_exceed counts t_b >= t (false for a NaN on either side), null_mean sums from 0.0 in ascending b
+    const GofReduceArgs red{dstat, dstat_b, dexceed, dmean, (int64_t)NP, B};
+    CK(sp.timed(2, [&]() -> int {
+        gof_launch_reduce(red, d.stream);
+        HIPCK(hipGetLastError());
+        return 0;
+    }));
+    CK(download(d, h_stat, dstat));
+    CK(download(d, h_f, df));
+    CK(download(d, h_nit, dnit));
+    CK(download(d, h_conv, dconv));
+    CK(download(d, h_Ha, dHa));
+    CK(download(d, h_Hb, dHb));
+    CK(download(d, h_Ha0, dHa0));
+    CK(download(d, h_Hb0, dHb0));
+    CK(download(d, h_exceed, dexceed));
+    CK(download(d, h_mean, dmean));
+    CK(download(d, h_stat_b, dstat_b));
+    CK(download(d, h_nit_b, dnit_b));
+    HIPCK(hipStreamSynchronize(d.stream));
+
+    // the compact problem list back into the (N, S, ...) results; a sample's free fits are those of its first tested problem (every
+    // tested problem of a pair solves the same two rows on C and holds the same bits)
+    for (size_t j = 0; j < NP; ++j) {
+        const size_t o = slot[j], n = (size_t)pair_n[j];
+        if (j == 0 || pair_n[j - 1] != pair_n[j]) {
+            std::copy(h_Ha.begin() + j * K, h_Ha.begin() + (j + 1) * K, exposures_a + n * K);
+            std::copy(h_Hb.begin() + j * K, h_Hb.begin() + (j + 1) * K, exposures_b + n * K);
+        }
+        statistic[o] = h_stat[j];
+        n_exceed[o] = h_exceed[j];
+        null_mean[o] = h_mean[j];
+        std::copy(h_Ha0.begin() + j * K, h_Ha0.begin() + (j + 1) * K, tied_exposures_a + o * K);
+        std::copy(h_Hb0.begin() + j * K, h_Hb0.begin() + (j + 1) * K, tied_exposures_b + o * K);
+        for (int i = 0; i < 4; ++i) errors[4 * o + i] = h_f[4 * j + i];
+        for (int i = 0; i < 3; ++i) n_iterations[3 * o + i] = h_nit[3 * j + i], converged[3 * o + i] = h_conv[3 * j + i];
+        for (size_t b = 0; b < (size_t)B; ++b) {
+            null_statistics[b * NS + o] = h_stat_b[b * NP + j];
+            for (int i = 0; i < 3; ++i) null_n_iterations[3 * (b * NS + o) + i] = h_nit_b[3 * (b * NP + j) + i];
+            if (draws)  // plain counts: the clipped zeros restored to 0
+                for (int i = 0; i < 2 * V; ++i) {
+                    const double c = h_draws[(b * NP + j) * 2 * V + i];
+                    draws[(b * NS + o) * 2 * V + i] = c < 1.0 ? 0.0 : c;
                 }
         }
     }
