@@ -241,6 +241,8 @@ def isolation(runs, max_kl_increase, rel=1e-6):
 #   "word2"     signatures 32..63: the set fills exactly the second mask word
 #   "prefix"    signatures 0..32 of 40: the sub-catalogue has the same KT and keeps every signature in its position
 #   "required"  "random", and of each sample's candidates a random third is required (at least one)
+#   "edge"      "random", and every sample holds the last signature and the first one of the last mask word, 32 floor((K - 1) / 32)
+#               (tests/test_gpu_family_edges.py)
 # At 20-step solves and the default threshold no re-addition trial of these inputs is accepted (the backward rounds only
 # remove what costs less than 1.92, and a signature that comes back gains about what it cost); the thresholds 0.1 and -0.01
 # are those at which the K = 33 and K = 96 cases accept one each, still isolated.
@@ -290,6 +292,9 @@ def case_sets(P, K, seed, sets):
         return np.arange(K) < 33, None
     C = random_rows(P)
     if sets == "random":
+        return C, None
+    if sets == "edge":
+        C[:, [K - 1, 32 * ((K - 1) // 32)]] = True
         return C, None
     R = np.zeros((P, K), dtype=bool)
     for p in range(P):

@@ -166,11 +166,14 @@ def gpu_case(K, V):
     """(counts_a, counts_b, signatures, candidates), computed once and never modified: Poisson counts of unequal totals from one
     catalogue, three zero-heavy rows in a; row totals (a, b) of pairs 0..5: (0, *), (1, 257), (2, 1), (257, 100 000), (100 000, 2),
     (*, 0); the last signature row has zeros (row a of pair 3 is drawn from it); an (N, K) mask in which pair 9 holds the dense
-    signature 1 alone, and every other set holds it too, so that no feature with counts is left without a signature."""
+    signature 1 alone, and every other set holds it too, so that no feature with counts is left without a signature.
+
+    A shape outside GPU_CASES (tests/test_gpu_family_edges.py) gets the candidate-word edge as well: every set but pair 9's also
+    holds signature K - 1 and signature 32 floor((K - 1) / 32).  The cases of GPU_CASES are what they were."""
     N = GPU_N
     rng = np.random.default_rng(1000 * K + V)
     Xa, W = refit_ref.poisson_catalogue(N, K, V=V, seed=70 + K, zero_heavy=3)
-    W[K - 1, rng.permutation(V)[: max(2, V // 3)]] = 0.0
+    W[K - 1, rng.permutation(V)[: min(max(2, V // 3), V - 1)]] = 0.0  # (the last signature keeps a feature at any V)
     W = refit_ref.normalize(W)
     E = rng.dirichlet(np.full(K, 0.3), size=N) * rng.uniform(50, 3000, size=(N, 1))
     Xb = rng.poisson(E @ W).astype(np.float64)
@@ -182,6 +185,8 @@ def gpu_case(K, V):
             Xb[row] = rng.multinomial(tb, uniform)
     C = rng.random((N, K)) < 0.8
     C[:, min(1, K - 1)] = True
+    if (K, V) not in GPU_CASES:
+        C[:, [K - 1, 32 * ((K - 1) // 32)]] = True
     C[:9] = True
     C[9] = False
     C[9, min(1, K - 1)] = True

@@ -209,9 +209,14 @@ GPU_FIXED = dict(min_iterations=40, max_iterations=40, conv_test_freq=10, tol=1e
 PERM_SEED = 7
 
 
+def edge_test(K):
+    """The tested signatures of a shape outside GPU_CASES: the first, bit 0 of the last candidate word and the last, K - 1."""
+    return tuple(sorted({0, 32 * ((K - 1) // 32), K - 1}))
+
+
 def gpu_case(K, V):
     """(counts_a, counts_b, signatures, candidates, test), never modified."""
-    return (*change_ref.gpu_case(K, V), GPU_TEST[K, V])
+    return (*change_ref.gpu_case(K, V), GPU_TEST[K, V] if (K, V) in GPU_TEST else edge_test(K))
 
 
 @functools.lru_cache(maxsize=None)

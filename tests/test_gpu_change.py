@@ -81,8 +81,9 @@ def test_observed_fits_are_the_three_masked_solves(K, V):
         assert np.array_equal(res.errors[rows, i], fit.reconstruction_errors), i
         assert np.array_equal(res.n_iterations[rows, i], fit.n_iterations) and np.array_equal(res.converged[rows, i], fit.converged), i
         assert (H[rows][~C[rows]] == 0.0).all()
-    assert 1 < np.unique(res.n_iterations[rows]).size  # problems of one tile stop at different tests
-    assert not res.converged[rows].all() and res.converged[rows].any()
+    if V > 1:  # (with one feature every solve sits at its fixed point after one step)
+        assert 1 < np.unique(res.n_iterations[rows]).size  # problems of one tile stop at different tests
+        assert not res.converged[rows].all() and res.converged[rows].any()
     with np.errstate(invalid="ignore"):
         assert np.array_equal(res.shares_a[rows], res.exposures_a[rows] / res.exposures_a[rows].sum(axis=1, keepdims=True))
         assert np.array_equal(res.shares_b[rows], res.exposures_b[rows] / res.exposures_b[rows].sum(axis=1, keepdims=True))
@@ -108,7 +109,8 @@ def test_draws_equal_the_replica(K, V):
     assert np.array_equal(res.draws, want)
     totals = np.where(res.tested[:, None], np.stack([Xa.sum(axis=1), Xb.sum(axis=1)], axis=1), 0.0)
     assert np.array_equal(res.draws.sum(axis=3), np.broadcast_to(totals, (B, N, 2)))
-    assert not np.array_equal(res.draws[0, 3, 0], res.draws[1, 3, 0]) and not np.array_equal(res.draws[0, 6, 0], res.draws[0, 6, 1])
+    if V > 1:  # (with one feature every draw is the row's total)
+        assert not np.array_equal(res.draws[0, 3, 0], res.draws[1, 3, 0]) and not np.array_equal(res.draws[0, 6, 0], res.draws[0, 6, 1])
 
 
 @pytest.mark.parametrize("K,V", CASES[1:])

@@ -162,7 +162,7 @@ def test_draws_equal_the_replica(K, V):
     totals = np.where(res.tested[:, :, None], np.stack([Xa.sum(axis=1), Xb.sum(axis=1)], axis=1)[:, None, :], 0.0)
     assert np.array_equal(res.draws.sum(axis=4), np.broadcast_to(totals, (B, N, len(test), 2)))
     n, j = 3, int(np.flatnonzero(res.tested[3])[0])
-    assert not np.array_equal(res.draws[0, n, j, 1], res.draws[1, n, j, 1])
+    assert V == 1 or not np.array_equal(res.draws[0, n, j, 1], res.draws[1, n, j, 1])  # (with one feature every draw is the row's total)
 
 
 @pytest.mark.parametrize("K,V", CASES)
