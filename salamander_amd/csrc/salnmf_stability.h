@@ -195,11 +195,28 @@ __global__ void __launch_bounds__(BLOCK) stability_kernel(StabArgs p) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) dst[((lane >> 4) + 4 * r) * STAB_TS + j] = 1.0 - acc[r];
             }
-            pm[j] = j;  // (a tile of non-finite costs may leave columns unmatched: the indices stay in range)
+            pm[j] = j < K ? -1 : j;
             __syncthreads();
             const int m = pass * STAB_PER_PASS + sub;
             const int pc = stab_assign(tl, K, j);
             if (pc >= 0 && pc < K && j < K) pm[pc] = j;
+            __syncthreads();
+            // A tile of non-finite costs may leave rows and columns unmatched (never one of finite costs).  Every lane
+            // stored its own column, so the entries that are set differ and as many columns as rows are left: the
+            // unmatched rows take them in ascending order.  p[m] is a permutation whatever the input, and a row that
+            // is not finite reaches the sums and the scores of a cluster instead of dropping out of them.
+            if (j == 0) {
+                unsigned taken = 0;
+                for (int r = 0; r < K; ++r)
+                    if (pm[r] >= 0) taken |= 1u << pm[r];
+                int c = 0;
+                for (int r = 0; r < K; ++r)
+                    if (pm[r] < 0) {
+                        while (c < K - 1 && (taken >> c & 1u)) ++c;
+                        pm[r] = c;
+                        if (c < K - 1) ++c;
+                    }
+            }
             __syncthreads();
             if (m < M) {
                 if (t > 1 && j < K && P[m * STAB_K + j] != pm[j]) flag[1] = 1;
@@ -288,7 +305,7 @@ __global__ void __launch_bounds__(BLOCK) stability_kernel(StabArgs p) {
         for (int c = 0; c < K; ++c) {
             const double z = p.cluster[(size_t)blockIdx.x * STAB_K + c];
             sum += z;
-            if (!(z >= lo)) lo = z;  // (a NaN wins: it is reported, not skipped)
+            if (lo == lo && !(z >= lo)) lo = z;  // (a NaN wins and stays: it is reported, not skipped)
         }
         p.score[2 * blockIdx.x] = sum / (double)K;
         p.score[2 * blockIdx.x + 1] = lo;

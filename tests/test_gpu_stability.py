@@ -244,3 +244,116 @@ def test_in_place_equals_stand_alone_bit_for_bit():
         check(in_place[g], ref.stability(np.stack([W[m] for m in groups[g]]), errors[g]), f"in place, group {g}")
         for f in FIELDS:
             assert np.array_equal(getattr(in_place[g], f), getattr(alone[g], f), equal_nan=True), (g, f)
+
+
+# ------------------------------------------------------------------ the assignment solve on constructed cost tiles
+# (tests/_stability_ref.py: block_group and the families on it; their properties are asserted in
+# tests/test_stability_solver_host.py)
+def same_bits(x, y, label=""):
+    for f in FIELDS:
+        assert np.array_equal(getattr(x, f), getattr(y, f), equal_nan=True), (label, f)
+
+
+@pytest.mark.parametrize("V", ref.HARD_VS)
+@pytest.mark.parametrize("K", ref.HARD_KS)
+@pytest.mark.parametrize("family", list(ref.HARD_FAMILIES))
+def test_hard_assignment_tiles(family, K, V):
+    """One anchor of block indicators and one member whose first-round cost tile is prescribed: Machol-Wien costs and the
+    chain tile (augmenting paths through all K columns), and a pair of optima 1e-6 .. 1e-4 apart."""
+    sigs, errors, want = ref.hard_case(family, K, V)
+    assert not ref.greedy_is_optimal(ref.first_tile(want))  # (a condition on the input: row minima do not solve it)
+    check(sal.signature_stability(np.array(sigs), np.array(errors)), want, f"{family} V={V}")
+
+
+@pytest.mark.parametrize("K,M", ref.DENSE_CASES)
+def test_random_dense_tiles_over_many_rounds(K, M):
+    sigs, errors, want = ref.hard_case("dense", K, M)
+    assert want.converged and want.n_rounds > 4
+    check(sal.signature_stability(np.array(sigs), np.array(errors), max_rounds=ref.DENSE_MAX_ROUNDS), want, "dense")
+
+
+def hard_groups():
+    cases = [ref.hard_case(f, K, 96) for f in ref.HARD_FAMILIES for K in (16, 15, 3)] + [ref.hard_case("dense", 16, 17), ref.hard_case("dense", 5, 65)]
+    return [np.array(c[0]) for c in cases], [np.array(c[1]) for c in cases], [c[2] for c in cases]
+
+
+def test_hard_groups_in_one_launch_equal_each_alone():
+    sigs, errors, _ = hard_groups()
+    together = sal.signature_stability(sigs, errors, max_rounds=ref.DENSE_MAX_ROUNDS)
+    for g, (s, e) in enumerate(zip(sigs, errors)):
+        same_bits(together[g], sal.signature_stability(s, e, max_rounds=ref.DENSE_MAX_ROUNDS), g)
+
+
+@pytest.mark.parametrize("K", ref.HARD_KS)
+def test_exact_tie_returns_one_of_the_optima(K):
+    """Two member rows of the same bits: each optimum has a twin of equal cost, and the host and the device round the tile
+    differently, so either may come back.  The twins give the same cluster sums, so the replica's last centroids price
+    the device's assignment."""
+    sigs, errors = ref.block_group([ref.exact_tie(K)], 96)
+    want = ref.stability(sigs, errors)
+    assert want.margins[1] == 0.0
+    got = sal.signature_stability(sigs, errors)
+    tol = 4 * (96 + 2 + 8) * 2.0**-52
+    for m in range(2):
+        assert sorted(got.assignments[m]) == list(range(K))
+        D = 1.0 - want.centroids @ want.unit[m].T
+        cost, best = D[np.arange(K), got.assignments[m]].sum(), D[np.arange(K), want.assignments[m]].sum()
+        print(f"exact tie K={K} member {m}: cost - optimum = {cost - best:.3g}, K tol = {K * tol:.3g}")
+        assert cost - best <= K * tol
+    assert 2 <= got.n_rounds <= 20 and (got.converged or got.n_rounds == 20)
+    same_bits(got, sal.signature_stability(sigs, errors))
+
+
+@pytest.mark.parametrize("V", ref.HARD_VS)
+def test_hard_members_in_place_equal_stand_alone_bit_for_bit(V):
+    cases = [ref.hard_case(f, K, V) for f in ref.HARD_FAMILIES for K in (16, 3)]
+    if V == 96:
+        cases.append(ref.hard_case("dense", 16, 17))
+    sigs, errors = [np.array(c[0]) for c in cases], [np.array(c[1]) for c in cases]
+    Ks = [s.shape[1] for s in sigs for _ in s]
+    rng = np.random.default_rng(6)
+    batch = BatchEngine(16, V, Ks)
+    try:
+        groups, m = [], 0
+        for s in sigs:
+            groups.append(list(range(m, m + len(s))))
+            for W in s:
+                batch.upload_member(m, W, rng.gamma(1.0, 100.0, size=(16, W.shape[0])))
+                m += 1
+        in_place = batch.stability(groups, errors, max_rounds=ref.DENSE_MAX_ROUNDS)
+    finally:
+        batch.close()
+    alone = sal.signature_stability(sigs, errors, max_rounds=ref.DENSE_MAX_ROUNDS)
+    for g, c in enumerate(cases):
+        check(in_place[g], c[2], f"hard, in place, group {g}")
+        same_bits(in_place[g], alone[g], g)
+
+
+@pytest.mark.parametrize("member", [0, 4])
+@pytest.mark.parametrize("kind", ["nan", "zero"])
+def test_a_signature_that_is_not_finite_in_place(kind, member):
+    """Only the in-place form can see one (a fit that failed): the stand-alone entry refuses it.  The kernel forms no
+    address from a cost: the solve's indices come from lane numbers and matched rows alone, and its result reaches memory
+    through the permutation, which the hand-off completes.  So the call returns, the group's assignments are permutations,
+    its minimum stability is NaN, and the healthy group of the same launch does not notice."""
+    K, M = 5, 6
+    healthy, _ = ref.planted(K, M, 96, 0.3, seed=21)
+    bad, _ = ref.planted(K, M, 96, 0.3, seed=22)
+    if kind == "nan":
+        bad[member, 2, 7] = np.nan  # (member 0 is the anchor: errors all zero)
+    else:
+        bad[member, 2] = 0.0
+    batch = BatchEngine(16, 96, [K] * (2 * M))
+    try:
+        for m, W in enumerate(np.concatenate([healthy, bad])):
+            batch.upload_member(m, W, np.ones((16, K)))
+        got = batch.stability([list(range(M)), list(range(M, 2 * M))])
+    finally:
+        batch.close()
+    assert got[1].assignments.shape == (M, K) and all(sorted(p) == list(range(K)) for p in got[1].assignments)
+    assert np.isnan(got[1].stability_min) and np.isnan(got[1].stability_mean)
+    assert 1 <= got[1].n_rounds <= 20 and (got[1].converged or got[1].n_rounds == 20)
+    check(got[0], ref.stability(healthy), "healthy neighbour")
+    same_bits(got[0], sal.signature_stability(healthy))
+    want = ref.lane_stability(bad)
+    print(f"{kind} in member {member}: rounds {got[1].n_rounds} (lane replica {want.n_rounds}), NaN clusters {int(np.isnan(got[1].cluster_stability).sum())} ({int(np.isnan(want.cluster_stability).sum())})")
