@@ -523,7 +523,11 @@ def test_weighted_steps_through_the_cooperative_leftover_tile(K, n_given, lhalf)
 @pytest.mark.parametrize("N,V,K", [(3000, 96, 50), (777, 83, 7), (1200, 288, 12)])
 def test_lazy_exposure_scale_of_the_initialisation(N, V, K):
     """``Engine.set_H_scale`` (normalize_WH's exposure side + clip, initialize.py:116-118, applied by the first pass that
-    rewrites H): every reader sees clip(H * scale) bit for bit, and the steps continue from exactly that state."""
+    rewrites H): every reader sees clip(H * scale) bit for bit, and the steps continue from exactly that state.
+
+    Three readers on three shapes with a scale that clips nothing; ``test_gpu_pending_scale.py`` holds every reader of H
+    (and every pass that drops the scale) to the materialised state, on floor states with scales that clip whole columns,
+    and behind MvNMF steps as well."""
     X, W0, H0 = orc.synthetic_problem(V, N, K, seed=N)
     scale = np.random.default_rng(1).uniform(0.2, 3.0, K)
     Hs = np.clip(H0 * scale[None, :], orc.EPSILON, None)
