@@ -441,6 +441,13 @@ int salnmf_batch_download_member(salnmf_batch* b, int member, double* W, double*
  * first signatures kept (0 <= n_given[i] < its n_signatures); one launch of n_active workgroups per 4 096 steps.  Members
  * not listed are left as they are. */
 int salnmf_batch_kl_step(salnmf_batch* b, int n_steps, int n_active, const int* members, const int* n_given);
+/* Per-sample weights of one member, as salnmf_set_weights gives them to an engine: weights_kl scales every sample's KL
+ * term, weights_lhalf is its l-half penalty weight (with it the step takes the penalised closed form of the exposure
+ * update, also where every entry is 0).  Each argument is n_samples doubles or NULL; NULL / NULL clears the member's
+ * weights.  Negative or non-finite entries are refused before anything is copied.  A weighted member's steps and queued
+ * objectives are, bit for bit, those of an engine with the same weights; salnmf_batch_samplewise_kl and _heldout_kl stay
+ * unweighted.  One salnmf_batch_kl_step call may list weighted and unweighted members together (two launches then). */
+int salnmf_batch_set_weights(salnmf_batch* b, int member, const double* weights_kl, const double* weights_lhalf);
 /* KLNMF.objective_function (klnmf.py:64-80, kl_divergence _utils_klnmf.py:11-55) of each listed member into row `slot` of
  * the objective array (pinned host memory, written by the reducing workgroup), no host round trip.  Entries of members not
  * listed keep what they held. */

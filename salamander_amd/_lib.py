@@ -113,6 +113,7 @@ SIGNATURES = {
     "salnmf_batch_upload_member": (c_int, [_P, c_int, _D, _D]),
     "salnmf_batch_download_member": (c_int, [_P, c_int, _D, _D]),
     "salnmf_batch_kl_step": (c_int, [_P, c_int, c_int, POINTER(c_int), POINTER(c_int)]),
+    "salnmf_batch_set_weights": (c_int, [_P, c_int, _D, _D]),
     "salnmf_batch_objective_async": (c_int, [_P, c_int, c_int, POINTER(c_int)]),
     "salnmf_batch_objective_read": (c_int, [_P, c_int, c_int, _D]),
     "salnmf_batch_samplewise_kl": (c_int, [_P, _D]),

@@ -143,6 +143,14 @@ class BatchEngine:
         _lib.check(self._lib.salnmf_batch_download_member(self._h, int(member), _ptr(W), _ptr(H)))
         return W, H
 
+    def set_weights(self, member: int, weights_kl=None, weights_lhalf=None):
+        """Per-sample weights of one member, as ``Engine.set_weights``: ``(N,)`` arrays or None; None / None clears them.
+        Finite, non-negative entries only.  The member's steps and queued objectives are then the weighted ones;
+        ``samplewise_kl`` and ``heldout_kl`` stay unweighted."""
+        wk = None if weights_kl is None else _as_c(weights_kl, (self.N,), "weights_kl")
+        wl = None if weights_lhalf is None else _as_c(weights_lhalf, (self.N,), "weights_lhalf")
+        _lib.check(self._lib.salnmf_batch_set_weights(self._h, int(member), None if wk is None else _ptr(wk), None if wl is None else _ptr(wl)))
+
     def kl_step(self, n_steps: int, members, n_given):
         """``n_steps`` joint updates of each listed member (``n_given[i]`` given signatures of ``members[i]``)."""
         m, g = _ints(members), _ints(n_given)

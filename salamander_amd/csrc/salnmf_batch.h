@@ -34,7 +34,12 @@ struct SmallBatchArgs {
     const int* __restrict__ active;   // [n_active]
     const int* __restrict__ n_given;  // [n_active]
     int V, ntiles, nsteps;
+    // per-sample weights (salnmf_batch_set_weights), a table beside the members that only the weighted kernel reads:
+    // entries 2 m and 2 m + 1 are member m's w_kl and w_lhalf as an engine holds them ([Np], pad rows 1 / 0), or null
+    const double* const* __restrict__ weights;
 };
-int launch_small_kl_batch(const SmallBatchArgs& a, int n_active, hipStream_t stream);
+// The first n_plain entries of the lists are members without weights and go through the unweighted kernel, the n_weighted
+// entries behind them through the weighted instantiation (small_kl_body<..., WTS = true>): at most two launches.
+int launch_small_kl_batch(const SmallBatchArgs& a, int n_plain, int n_weighted, hipStream_t stream);
 
 }  // namespace salnmf

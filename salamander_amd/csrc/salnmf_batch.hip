@@ -44,11 +44,15 @@ struct BatchFwdArgs {
     // exposure scale H is read with, as clip(H * hscale)
     const double* const* __restrict__ xover;
     const double* __restrict__ hscale;
+    // mode 0: the weight table of the batched step (salnmf_batch.h: SmallBatchArgs::weights); null for mode 1
+    const double* const* __restrict__ weights;
 };
 
 // forward_body<KS, MODE> (salnmf_forward_kernel.h) for one member with the parameters an engine of <= 16 signatures and
 // <= 96 features passes for salnmf_objective_async (mode 0, the in-launch sum) and salnmf_samplewise_kl (mode 1):
-// the member's own dataset, unweighted, no pending exposure scale, one feature block, one signature chunk.  Members of
+// the member's own dataset, no pending exposure scale, one feature block, one signature chunk; mode 0 with the member's
+// weights (salnmf_batch_set_weights: the weighted KL and the l-half penalty of an engine's objective), mode 1 always
+// unweighted, as salnmf_samplewise_kl.  Members of
 // 1-4, 5-8 and 9-16 signatures share the launch (KS = 1, 2, 4; the branch is uniform per workgroup, LDS is sized for the
 // widest).
 template <int MODE>
@@ -69,6 +73,8 @@ __global__ void __launch_bounds__(BLOCK, 2) batch_forward_kernel(BatchFwdArgs a)
     p.K = b.K;
     p.ntiles = a.ntiles;
     if (MODE == 0) {
+        p.wkl = a.weights[2 * m];
+        p.wlh = a.weights[2 * m + 1];
         p.sum_out = a.sum_out + m;
         p.sum_counter = a.counter + m;
     }
@@ -107,6 +113,10 @@ struct salnmf_batch {
     int F = 0;  // count splitting (salnmf_batch_split): train split f is dataset f, test split f dataset F + f
     std::vector<int> dataset;
     bool members_dirty = false;
+    // per-member weights (salnmf_batch_set_weights): device arrays of Np doubles, pad rows 1 / 0, null without weights;
+    // entries 2 m, 2 m + 1 = member m's w_kl, w_lhalf.  dweights is the device's copy, rewritten with the member table
+    std::vector<double*> weights;
+    const double** dweights = nullptr;
 };
 
 // the device's member table follows the host's once the launches that read the old one are done
@@ -114,6 +124,7 @@ static int flush_members(salnmf_batch* b) {
     if (!b->members_dirty) return 0;
     HIPCK(hipStreamSynchronize(b->stream));
     HIPCK(hipMemcpy(b->dmembers, b->members.data(), b->members.size() * sizeof(BatchMember), hipMemcpyHostToDevice));
+    HIPCK(hipMemcpy(b->dweights, b->weights.data(), b->weights.size() * sizeof(double*), hipMemcpyHostToDevice));
     b->members_dirty = false;
     return 0;
 }
@@ -491,6 +502,7 @@ int salnmf_batch_create(int device, int n_features, int64_t n_samples, int n_mem
     b->fgrid = forward_grid(prop.multiProcessorCount, b->ntiles);
     b->K.assign(n_signatures, n_signatures + n_members);
     b->dataset.assign((size_t)n_members, -1);
+    b->weights.assign((size_t)2 * n_members, nullptr);
     auto cleanup = [&](int rc) {
         salnmf_batch_destroy(b);
         return rc;
@@ -504,7 +516,7 @@ int salnmf_batch_create(int device, int n_features, int64_t n_samples, int n_mem
         hipMalloc(&b->state, state * sizeof(double)) != hipSuccess || hipMalloc(&b->part, (size_t)b->M * b->fgrid * sizeof(double)) != hipSuccess ||
         hipMalloc(&b->klout, (size_t)b->M * b->Np * sizeof(double)) != hipSuccess || hipMalloc(&b->counter, (size_t)b->M * sizeof(unsigned)) != hipSuccess ||
         hipMalloc(&b->dmembers, (size_t)b->M * sizeof(BatchMember)) != hipSuccess || hipMalloc(&b->dstep, (size_t)2 * b->M * sizeof(int)) != hipSuccess ||
-        hipMalloc(&b->dobj, (size_t)b->M * sizeof(int)) != hipSuccess)
+        hipMalloc(&b->dobj, (size_t)b->M * sizeof(int)) != hipSuccess || hipMalloc(&b->dweights, (size_t)2 * b->M * sizeof(double*)) != hipSuccess)
         return cleanup(fail("hipMalloc failed (batch of %d members)", n_members));
     if (hipHostMalloc(&b->pin, (size_t)SALNMF_BATCH_SLOTS * b->M * sizeof(double), hipHostMallocPortable) != hipSuccess)
         return cleanup(fail("hipHostMalloc failed"));
@@ -520,7 +532,7 @@ int salnmf_batch_create(int device, int n_features, int64_t n_samples, int n_mem
         H += hsz;
     }
     if (hipMemcpy(b->dmembers, b->members.data(), b->members.size() * sizeof(BatchMember), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemset(b->counter, 0, (size_t)b->M * sizeof(unsigned)) != hipSuccess || hipMemset(b->state, 0, state * sizeof(double)) != hipSuccess)
+        hipMemset(b->counter, 0, (size_t)b->M * sizeof(unsigned)) != hipSuccess || hipMemset(b->dweights, 0, (size_t)2 * b->M * sizeof(double*)) != hipSuccess || hipMemset(b->state, 0, state * sizeof(double)) != hipSuccess)
         return cleanup(fail("hipMemcpy failed"));
     *out = b;
     return 0;
@@ -535,6 +547,9 @@ void salnmf_batch_destroy(salnmf_batch* b) {
     for (void* p : {(void*)b->X, (void*)b->xlx, (void*)b->Xr, (void*)b->xlxr, (void*)b->state, (void*)b->part, (void*)b->klout, (void*)b->counter, (void*)b->dmembers, (void*)b->dstep,
                     (void*)b->dobj})
         if (p) (void)hipFree(p);
+    for (double* w : b->weights)
+        if (w) (void)hipFree(w);
+    if (b->dweights) (void)hipFree(b->dweights);
     if (b->pin) (void)hipHostFree(b->pin);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
@@ -594,6 +609,38 @@ int salnmf_batch_download_member(salnmf_batch* b, int member, double* W, double*
     return 0;
 }
 
+int salnmf_batch_set_weights(salnmf_batch* b, int member, const double* weights_kl, const double* weights_lhalf) {
+    CK(check_member(b, member));
+    for (const double* w : {weights_kl, weights_lhalf})
+        for (int64_t n = 0; w && n < b->N; ++n)
+            if (!(w[n] >= 0.0) || !std::isfinite(w[n]))
+                return fail("member %d: %s must be finite and non-negative, entry %lld is %g", member, w == weights_kl ? "weights_kl" : "weights_lhalf",
+                            (long long)n, w[n]);
+    HIPCK(hipSetDevice(b->device));
+    HIPCK(hipStreamSynchronize(b->stream));  // (the launches that read the old arrays are done)
+    auto set = [&](double*& dev, const double* host, double filler) -> int {
+        if (!host) {
+            double* old = dev;
+            dev = nullptr;  // (first: a failing hipFree must not leave the pointer behind)
+            if (old) HIPCK(hipFree(old));
+            return 0;
+        }
+        if (!dev && hipMalloc(&dev, (size_t)b->Np * sizeof(double)) != hipSuccess) {
+            dev = nullptr;
+            return fail("hipMalloc failed (weights of member %d)", member);
+        }
+        std::vector<double> padded((size_t)b->Np, filler);  // as salnmf_set_weights pads an engine's
+        std::copy(host, host + b->N, padded.begin());
+        HIPCK(hipMemcpy(dev, padded.data(), padded.size() * sizeof(double), hipMemcpyHostToDevice));
+        return 0;
+    };
+    // the member table follows in either case: a failure below leaves the member with the arrays it still has
+    const int rc_kl = set(b->weights[(size_t)2 * member], weights_kl, 1.0);
+    const int rc_lh = rc_kl ? rc_kl : set(b->weights[(size_t)2 * member + 1], weights_lhalf, 0.0);
+    b->members_dirty = true;  // (the weight table is rewritten with the member table, like point_member's change)
+    return rc_lh;
+}
+
 int salnmf_batch_kl_step(salnmf_batch* b, int n_steps, int n_active, const int* members, const int* n_given) {
     if (!b) return fail("null batch");
     CK(check_list(b, n_active, members));
@@ -602,20 +649,32 @@ int salnmf_batch_kl_step(salnmf_batch* b, int n_steps, int n_active, const int* 
     if (!b->x_ok) return fail("upload X first");
     if (!n_given) return fail("null n_given");
     HIPCK(hipSetDevice(b->device));
-    std::vector<int> want(members, members + n_active);
     for (int i = 0; i < n_active; ++i) {
         const int K = b->K[(size_t)members[i]];
         if (n_given[i] < 0 || n_given[i] >= K)
             return fail("member %d: n_given must be in [0, %d), got %d (all signatures given: nothing to step)", members[i], K, n_given[i]);
-        want.push_back(n_given[i]);
     }
+    // the members without weights first (today's kernel), the weighted ones behind them (its weighted instantiation), each
+    // part in the caller's order: [members | their n_given]
+    auto weighted = [&](int m) { return b->weights[(size_t)2 * m] || b->weights[(size_t)2 * m + 1]; };
+    std::vector<int> order;
+    for (int pass = 0; pass < 2; ++pass)
+        for (int i = 0; i < n_active; ++i)
+            if (weighted(members[i]) == (pass == 1)) order.push_back(i);
+    int n_plain = 0;
+    std::vector<int> want;
+    for (int i : order) {
+        want.push_back(members[i]);
+        n_plain += !weighted(members[i]);
+    }
+    for (int i : order) want.push_back(n_given[i]);
     CK(set_list(b, b->dstep, b->step_list, want));
     CK(flush_members(b));
-    SmallBatchArgs a{b->dmembers, b->dstep, b->dstep + n_active, b->V, (int)b->ntiles, 0};
+    SmallBatchArgs a{b->dmembers, b->dstep, b->dstep + n_active, b->V, (int)b->ntiles, 0, b->dweights};
     constexpr int kMaxPerLaunch = 4096;  // (salnmf_kl_step's bound on one launch of the small kernel)
     for (int i = 0; i < n_steps; i += a.nsteps) {
         a.nsteps = std::min(kMaxPerLaunch, n_steps - i);
-        if (launch_small_kl_batch(a, n_active, b->stream)) return fail("no batched small-cohort kernel for %lld tiles", (long long)b->ntiles);
+        if (launch_small_kl_batch(a, n_plain, n_active - n_plain, b->stream)) return fail("no batched small-cohort kernel for %lld tiles", (long long)b->ntiles);
         HIPCK(hipGetLastError());
     }
     return 0;
@@ -631,7 +690,7 @@ int salnmf_batch_objective_async(salnmf_batch* b, int slot, int n_active, const 
     if (n_active > 0) {
         CK(set_list(b, b->dobj, b->obj_list, std::vector<int>(members, members + n_active)));
         CK(flush_members(b));
-        BatchFwdArgs a{b->dmembers, b->dobj, b->part, b->counter, b->pin + (size_t)slot * b->M, b->N, b->ntiles, b->V};
+        BatchFwdArgs a{b->dmembers, b->dobj, b->part, b->counter, b->pin + (size_t)slot * b->M, b->N, b->ntiles, b->V, nullptr, nullptr, b->dweights};
         hipLaunchKernelGGL(batch_forward_kernel<0>, dim3(b->fgrid, n_active), dim3(BLOCK), 0, b->stream, a);
         HIPCK(hipGetLastError());
     }

@@ -640,6 +640,7 @@ struct EpiGeo {
 
 // H update with an l-half penalty (_utils_klnmf.py:349-361): I = 4 H (W^T aux) [w_kl^2]; D = w_lh^2 / 4 + I;
 // H' = (w_lh / 2 - sqrt(D))^2 / 4 [/ w_kl^2]  (the cooperative tile's form of the statements in process_tile)
+// (salnmf_small.hip restates these statements at its weighted H update, with the contraction of D spelled out: keep the two alike)
 __device__ __forceinline__ double lhalf_update(double h, double u, double wl, double wk, bool has_wkl) {
     const double wk2 = wk * wk;
     double inter = 4.0 * h * u;

@@ -36,8 +36,10 @@ inline int forward_grid(int cus, int64_t ntiles) { return (int)std::min<int64_t>
 // xlogx_lane_kernel (salnmf_plain_kernels.h, compiled into salnmf.hip) over X [Np][VMAX] -> c [Np][16]
 void launch_xlogx_lane(const double* X, int64_t Np, int V, double* c, hipStream_t stream);
 
-// Small cohorts (salnmf_small.hip): n_steps joint KL steps of an unweighted problem with at most SMALL_MAX_TILES tiles and
-// 16 signatures in ONE one-workgroup launch; same bits as the per-step path.  0 = launched, 1 = shape not covered.
+// Small cohorts (salnmf_small.hip): n_steps joint KL steps of a problem with at most SMALL_MAX_TILES tiles and 16
+// signatures in ONE one-workgroup launch; same bits as the per-step path.  0 = launched, 1 = shape not covered.
+// The weighted instantiation of the kernel's body is reached by the batched launch alone (salnmf_batch.h), which hands it the
+// weights beside these parameters: grown by two pointers, this struct cost the unweighted batched kernel its global loads.
 constexpr int SMALL_MAX_TILES = 64;
 struct SmallParams {
     const double* __restrict__ X;  // [Np][VMAX]

@@ -1,5 +1,7 @@
-// Small cohorts: the joint KL step (update_WH, _utils_klnmf.py:281-347, unweighted) for up to 64 tiles (1 024 samples),
-// n_signatures <= 16, as ONE workgroup that runs n_steps steps per launch.
+// Small cohorts: the joint KL step (update_WH, _utils_klnmf.py:281-361) for up to 64 tiles (1 024 samples),
+// n_signatures <= 16, as ONE workgroup that runs n_steps steps per launch.  Unweighted for a single engine and for the
+// sweep's plain members; the weighted instantiation (WTS: per-sample KL weights and the l-half penalty, below) serves the
+// sweep's weighted members (salnmf_batch.h) -- a single weighted engine keeps the per-step path.
 //
 // At the size of the reference's own data set (data/pcawg_breast_sbs.csv: 192 samples, 5 signatures) the per-step path
 // is two launches per step -- fused_kernel on 3 workgroups + tail_kernel -- each shorter than its dispatch: 13.5 us per
@@ -18,6 +20,16 @@
 // tail_row's arithmetic for all rows at once.  Per entry the arithmetic of a tile is process_tile's (same MFMA chains,
 // same division sequence), so W, H and G come out bit for bit as from salnmf_kl_step's other path
 // (tests/test_gpu_small.py compares them).
+//
+// WTS = true honours the weight vectors handed in beside p as fused_kernel<..., WTS> does: the A operand of T = Ht^T R is H times w_kl of its row
+// (process_tile: ga *= wk, before the MFMAs), U = R W^T and the W tail are untouched, and with w_lhalf the H update is the
+// penalised closed form clip(lhalf_update(h, u, w_lhalf, w_kl), EPSILON) (its statements, restated at the update); with w_kl alone it stays the plain product.  A
+// lane's weights are those of its accumulator rows q + 4r -- the rows of h[] -- so they live in eight registers beside
+// h[]: resident across the steps when the wave has one tile and the workgroup at most two groups, fetched per tile from L2
+// where they are used otherwise (sixteen or twelve waves leave no registers for them).
+// They do not go to LDS: small_lds_doubles<4>() is at the 160 KB limit.  WTS = false compiles to the unweighted body's
+// instructions: every weighted statement sits behind `if (WTS)` (tests/test_gpu_small_weighted.py holds the weighted
+// members to the per-step path's bits and the plain ones of a mixed call to a batch that never saw weights).
 #define SALNMF_TEMPLATES_ONLY 1
 #include "salnmf_launch.h"
 #include "salnmf_batch.h"
@@ -38,8 +50,8 @@ constexpr int small_lds_doubles() { return 16 * WS + 4 * NG * SM_REGION; }
 
 // The body of one model's n_steps steps, shared by the single-model kernel and the batched one (one model per workgroup):
 // the same instructions, hence the same bits.  `lds` is the workgroup's small_lds_doubles<NG>() doubles.
-template <int KS, int NG, bool MULTI>
-__device__ __forceinline__ void small_kl_body(SmallParams p, double* lds) {
+template <int KS, int NG, bool MULTI, bool WTS>
+__device__ __forceinline__ void small_kl_body(SmallParams p, double* lds, const double* wkl_in = nullptr, const double* wlh_in = nullptr) {
     constexpr int NW = 4 * NG, NT = 64 * NW;
     static_assert(KS <= 4, "n_signatures <= 16: one signature tile");
     static_assert(!MULTI || NG == 4, "several tiles per wave only in the full workgroup");
@@ -63,7 +75,29 @@ __device__ __forceinline__ void small_kl_body(SmallParams p, double* lds) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) h[r] = p.H[((int64_t)t * 16 + q + 4 * r) * SM_KP + c16];
     };
+    // (WTS) w_kl and w_lhalf of the same rows; absent vectors read as 1 / 0 and are never used
+    const double* __restrict__ const wkl = WTS ? wkl_in : nullptr;  // [Np], 1 on pad rows, or null
+    const double* __restrict__ const wlh = WTS ? wlh_in : nullptr;  // [Np], 0 on pad rows, or null
+    double wk[4] = {1.0, 1.0, 1.0, 1.0}, wl[4] = {0.0, 0.0, 0.0, 0.0};
+    // Resident beside h[] only in the workgroups of one or two groups (256 registers a wave).  With three or four groups
+    // (168 / 128 registers) they are fetched inside the tile where they are used, from L2: w_kl ahead of the U product,
+    // which hides the load in front of T, w_lhalf behind T's MFMAs, once the ratio tile's 48 registers are free.
+    constexpr bool wres = WTS && resident && NG <= 2;
+    auto load_wk = [&](int t) __attribute__((always_inline)) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (wkl) wk[r] = wkl[t * 16 + q + 4 * r];
+    };
+    auto load_wl = [&](int t) __attribute__((always_inline)) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (wlh) wl[r] = wlh[t * 16 + q + 4 * r];
+    };
     if (resident && wave < ntiles) load_h(wave);
+    if (wres && wave < ntiles) {
+        load_wk(wave);
+        load_wl(wave);
+    }
     __syncthreads();
 
     // accumulator tiles vt = 0..5 of the numerator; virtual wave o owns the tiles vt = o, o + 4 (fused_kernel: tile t is
@@ -128,6 +162,7 @@ __device__ __forceinline__ void small_kl_body(SmallParams p, double* lds) {
                 // (48 features) at a time (A = R[n = c16][v = 4s + q], B = W[k = c16][v = 4s + q])
                 d4 u = (d4){0, 0, 0, 0};
                 const double* wu = Wl + c16 * WS + q;
+                if (WTS && !wres) load_wk(t);
 #pragma unroll
                 for (int half = 0; half < 2; ++half) {
 #pragma unroll
@@ -145,15 +180,34 @@ __device__ __forceinline__ void small_kl_body(SmallParams p, double* lds) {
                 double ga[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) ga[r] = Hl[(4 * r + q) * SM_LS + c16];
+                if (WTS && wkl) {  // (w_kl . Ht)^T . R: the weight of row 4r + q, as process_tile applies it
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) ga[r] *= wk[r];
+                }
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
 #pragma unroll
                     for (int vt = 0; vt < VT; ++vt) g[vt] = mfma(ga[r], pr[vt][r], g[vt]);
-                // ---- H update (_utils_klnmf.py:343-347); the tile stays in registers when it is this wave's only one
+                if (WTS && !wres) load_wl(t);
+                // ---- H update (_utils_klnmf.py:343-361); the tile stays in registers when it is this wave's only one
                 double* hdst = p.H + ((int64_t)t * 16 + q) * SM_KP + c16;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    h[r] = clip_lo(h[r] * u[r], kEps);
+                    if (WTS && wlh) {
+                        // lhalf_update's statements (salnmf_kernels.h) with the one contraction spelled out: in fused_kernel
+                        // w_kl's presence is a select in front of the sum, which leaves fma(0.25 wl, wl, inter) as the only
+                        // contraction; here the loop is cloned per presence, and the clone without w_kl could fuse 4 h u
+                        // into the sum instead
+                        const double wk2 = wk[r] * wk[r];
+                        double inter = 4.0 * h[r] * u[r];
+                        if (wkl) inter *= wk2;
+                        const double disc = __builtin_fma(0.25 * wl[r], wl[r], inter);
+                        const double t = wl[r] / 2 - sqrt(disc);
+                        double hn = 0.25 * (t * t);
+                        if (wkl) hn /= wk2;
+                        h[r] = clip_lo(hn, kEps);
+                    } else
+                        h[r] = clip_lo(h[r] * u[r], kEps);
                     if (!resident || last_step) hdst[4 * r * SM_KP] = h[r];
                 }
             }
@@ -269,24 +323,28 @@ __device__ __forceinline__ void small_kl_body(SmallParams p, double* lds) {
 template <int KS, int NG, bool MULTI>
 __global__ void __launch_bounds__(256 * NG, 1) small_kl_kernel(SmallParams p) {
     __shared__ __attribute__((aligned(16))) double lds[small_lds_doubles<NG>()];
-    small_kl_body<KS, NG, MULTI>(p, lds);
+    small_kl_body<KS, NG, MULTI, false>(p, lds);
 }
 
 // KLNMFSweep (salnmf_batch.h): workgroup i runs the steps of member a.active[i] -- the single-model kernel's body on that
 // member's W, H, numerator and dataset.  Members of different signature counts share the launch: the contraction depth
 // is picked per workgroup (the branch is uniform), LDS does not depend on it and the registers are those of the widest.
-template <int NG, bool MULTI>
+// WTS: the launch of the weighted members, a kernel of its own, so that the unweighted one's registers and code do not
+// depend on the weighted statements; it never reads the weight table.
+template <int NG, bool MULTI, bool WTS>
 __global__ void __launch_bounds__(256 * NG, 1) small_kl_batch_kernel(SmallBatchArgs a) {
     __shared__ __attribute__((aligned(16))) double lds[small_lds_doubles<NG>()];
     const int m = a.active[blockIdx.x];
     const BatchMember& b = a.members[m];
     const SmallParams p{b.X, b.H, b.W, b.W, b.G, a.V, b.K, a.ntiles, a.nsteps, a.n_given[blockIdx.x], 0 /* SALNMF_CLIP_ALL */};
+    const double* const wkl = WTS ? a.weights[2 * m] : nullptr;
+    const double* const wlh = WTS ? a.weights[2 * m + 1] : nullptr;
     if (b.K <= 4)
-        small_kl_body<1, NG, MULTI>(p, lds);
+        small_kl_body<1, NG, MULTI, WTS>(p, lds, wkl, wlh);
     else if (b.K <= 8)
-        small_kl_body<2, NG, MULTI>(p, lds);
+        small_kl_body<2, NG, MULTI, WTS>(p, lds, wkl, wlh);
     else
-        small_kl_body<4, NG, MULTI>(p, lds);
+        small_kl_body<4, NG, MULTI, WTS>(p, lds, wkl, wlh);
 }
 
 template <int KS>
@@ -308,19 +366,34 @@ int launch_ks(const SmallParams& p, hipStream_t stream) {
 
 }  // namespace
 
-int launch_small_kl_batch(const SmallBatchArgs& a, int n_active, hipStream_t stream) {
-    if (a.ntiles < 1 || a.ntiles > SMALL_MAX_TILES || n_active < 1) return 1;
+namespace {
+
+template <bool WTS>
+void launch_batch_part(const SmallBatchArgs& a, int n_active, hipStream_t stream) {
     const dim3 g(n_active);
     switch (std::min(4, (a.ntiles + 3) / 4)) {  // (the single-model launch's choice of NG)
-        case 1: hipLaunchKernelGGL((small_kl_batch_kernel<1, false>), g, dim3(256), 0, stream, a); break;
-        case 2: hipLaunchKernelGGL((small_kl_batch_kernel<2, false>), g, dim3(512), 0, stream, a); break;
-        case 3: hipLaunchKernelGGL((small_kl_batch_kernel<3, false>), g, dim3(768), 0, stream, a); break;
+        case 1: hipLaunchKernelGGL((small_kl_batch_kernel<1, false, WTS>), g, dim3(256), 0, stream, a); break;
+        case 2: hipLaunchKernelGGL((small_kl_batch_kernel<2, false, WTS>), g, dim3(512), 0, stream, a); break;
+        case 3: hipLaunchKernelGGL((small_kl_batch_kernel<3, false, WTS>), g, dim3(768), 0, stream, a); break;
         default:
             if (a.ntiles <= 16)
-                hipLaunchKernelGGL((small_kl_batch_kernel<4, false>), g, dim3(1024), 0, stream, a);
+                hipLaunchKernelGGL((small_kl_batch_kernel<4, false, WTS>), g, dim3(1024), 0, stream, a);
             else
-                hipLaunchKernelGGL((small_kl_batch_kernel<4, true>), g, dim3(1024), 0, stream, a);
+                hipLaunchKernelGGL((small_kl_batch_kernel<4, true, WTS>), g, dim3(1024), 0, stream, a);
             break;
+    }
+}
+
+}  // namespace
+
+int launch_small_kl_batch(const SmallBatchArgs& a, int n_plain, int n_weighted, hipStream_t stream) {
+    if (a.ntiles < 1 || a.ntiles > SMALL_MAX_TILES || n_plain < 0 || n_weighted < 0 || n_plain + n_weighted < 1) return 1;
+    if (n_plain > 0) launch_batch_part<false>(a, n_plain, stream);
+    if (n_weighted > 0) {
+        SmallBatchArgs w = a;
+        w.active += n_plain;
+        w.n_given += n_plain;
+        launch_batch_part<true>(w, n_weighted, stream);
     }
     return 0;
 }

@@ -25,6 +25,12 @@ times on the device into independent train and test halves, member (K, seed, f) 
 bit the single fit on that matrix -- and is scored against ``test_splits_[f]`` with its exposures scaled by
 ``(1 - p) / p``, all batched members in one launch of the forward pass (``BatchEngine.heldout_kl``).
 ``suggest_n_signatures_heldout`` returns the K of smallest mean held-out divergence.
+
+``lhalf_weights=[...]`` adds the l-half sparsity penalty as an axis of its own and ``weights_kl`` per-sample KL weights
+shared by all members: member (K, penalty, seed, r) is bit for bit the single fit with
+``fitting_kwargs={"weights_kl": weights_kl, "weights_lhalf": penalty}``, run in the weighted instantiation of the batched
+step (``BatchEngine.set_weights``).  With ``n_splits`` the penalty is chosen like K, by held-out likelihood
+(``suggest_penalty_heldout``).
 """
 
 from __future__ import annotations
@@ -82,7 +88,17 @@ class KLNMFSweep:
     nothing of the test half enters the selection -- and ``heldout_mean_`` / ``heldout_sem_`` ``(len(ns_signatures),)``
     are the mean of its held-out error over f and ``std(ddof=1) / sqrt(F)`` (NaN at F = 1).
     ``timings_["split_s"]`` and ``timings_["heldout_s"]`` are the time of the draw and of the scoring.  With
-    ``stability=True`` the members of a K count as seeds x splits."""
+    ``stability=True`` the members of a K count as seeds x splits.
+
+    ``lhalf_weights`` (a non-empty sequence of L finite, non-negative floats; not together with ``stability=True``) adds a
+    penalty axis: the members are K-major, then penalty, then seed, then resample / split minor, ``lhalf_of_`` holds the
+    penalty index per member (-1 without the axis), ``reconstruction_errors_`` and ``heldout_errors_`` are
+    ``(len(ns_signatures), L, seeds[, R or F])`` and ``heldout_mean_`` / ``heldout_sem_`` ``(len(ns_signatures), L)``, the
+    seed of smallest training error being taken per (K, penalty, f).  A penalty of 0.0 is the penalised closed form at zero
+    weight -- what a single fit with ``weights_lhalf=0.0`` runs -- not the unpenalised member.  ``weights_kl`` (a scalar,
+    list or ``(n_obs,)`` array, validated at ``fit`` as a single fit validates it) is shared by all members and allowed
+    without the axis.  Held-out scoring stays unweighted.  Without either, every attribute, shape and member order is as
+    above."""
 
     def __init__(
         self,
@@ -103,6 +119,8 @@ class KLNMFSweep:
         n_splits: int = 0,
         train_fraction: float = 0.5,
         split_seed: int = 0,
+        lhalf_weights=None,
+        weights_kl=None,
     ):
         ns = list(ns_signatures)
         if not ns or not all(isinstance(k, (int, np.integer)) and not isinstance(k, bool) and k > 0 for k in ns):
@@ -124,6 +142,19 @@ class KLNMFSweep:
         self.stability_max_rounds = check_max_rounds(stability_max_rounds)
         if self.stability and max(1, len(self.seeds or [])) * max(1, self.n_resamples) * max(1, self.n_splits) < 2:
             raise ValueError("'stability=True' needs at least two members per number of signatures: several seeds, or n_resamples >= 2.")
+        if lhalf_weights is not None:
+            try:
+                penalties = [float(v) for v in lhalf_weights]
+            except TypeError:
+                raise ValueError("'lhalf_weights' must be a non-empty sequence of finite, non-negative floats.") from None
+            if not penalties or not all(np.isfinite(v) and v >= 0.0 for v in penalties):
+                raise ValueError("'lhalf_weights' must be a non-empty sequence of finite, non-negative floats.")
+            if self.stability:
+                raise ValueError("'stability=True' is not supported together with 'lhalf_weights': grouping per (K, penalty) is not built.")
+            self.lhalf_weights = penalties
+        else:
+            self.lhalf_weights = None
+        self.weights_kl = weights_kl
         self.init_method = init_method
         self.min_iterations = min_iterations
         self.max_iterations = max_iterations
@@ -139,9 +170,11 @@ class KLNMFSweep:
         self.train_splits_ = None
         self.test_splits_ = None
         self.split_of_ = np.zeros(0, dtype=int)
+        self.lhalf_of_ = np.zeros(0, dtype=int)
         self.heldout_errors_ = np.zeros((0, 0, 0))
-        self.heldout_mean_ = np.full(len(self.ns_signatures), np.nan)
-        self.heldout_sem_ = np.full(len(self.ns_signatures), np.nan)
+        summary = (len(self.ns_signatures), len(self.lhalf_weights)) if self.lhalf_weights else len(self.ns_signatures)
+        self.heldout_mean_ = np.full(summary, np.nan)
+        self.heldout_sem_ = np.full(summary, np.nan)
         self._fitted = False
         self.timings_: dict[str, float] = {}
         self.member_steps_ = 0
@@ -155,15 +188,23 @@ class KLNMFSweep:
         )
 
     def _members(self, init_kwargs):
-        """``(K, init_kwargs of the member, resample or split of the member or -1)`` in K-major, seed-middle, resample-minor
-        (split-minor) order."""
+        """``(K, init_kwargs of the member, resample or split of the member or -1, penalty index or -1)`` in K-major, then
+        penalty, then seed, then resample-minor (split-minor) order."""
         base = {} if init_kwargs is None else dict(init_kwargs)
         resamples = range(self.n_resamples) if self.n_resamples else range(self.n_splits) if self.n_splits else [-1]
         out = []
+        penalties = range(len(self.lhalf_weights)) if self.lhalf_weights else [-1]
         for k in self.ns_signatures:
-            for kwargs in [base | {"seed": s} for s in self.seeds] if self.seeds else [init_kwargs]:
-                out.extend((k, kwargs, r) for r in resamples)
+            for l in penalties:
+                for kwargs in [base | {"seed": s} for s in self.seeds] if self.seeds else [init_kwargs]:
+                    out.extend((k, kwargs, r, l) for r in resamples)
         return out
+
+    def _fitting_kwargs(self, l: int):
+        """The ``fitting_kwargs`` of the single fit a member equals: None without weights, as today."""
+        if l < 0 and self.weights_kl is None:
+            return None
+        return {"weights_kl": self.weights_kl, "weights_lhalf": self.lhalf_weights[l] if l >= 0 else None}
 
     def _member_adata(self, adata, r: int):
         """The member's own copy of the data: the caller's, or resample r (train split r) under the caller's obs / var names."""
@@ -240,27 +281,51 @@ class KLNMFSweep:
             engine.close()
 
     def _summarise_heldout(self, train_errors: np.ndarray, heldout_errors: np.ndarray) -> None:
-        """``heldout_mean_`` / ``heldout_sem_`` from ``(len(ns), seeds, F)`` training and held-out errors: per (K, f) the
-        seed of smallest training error, lowest index on ties."""
-        F = heldout_errors.shape[2]
-        best = np.argmin(train_errors, axis=1)  # (the first of equal minima)
-        chosen = np.take_along_axis(heldout_errors, best[:, None, :], axis=1)[:, 0, :]
-        self.heldout_mean_ = chosen.mean(axis=1)
-        self.heldout_sem_ = chosen.std(axis=1, ddof=1) / np.sqrt(F) if F > 1 else np.full(len(chosen), np.nan)
+        """``heldout_mean_`` / ``heldout_sem_`` from ``(len(ns), [L,] seeds, F)`` training and held-out errors: per (K, f)
+        -- per (K, penalty, f) -- the seed of smallest training error, lowest index on ties."""
+        F = heldout_errors.shape[-1]
+        best = np.argmin(train_errors, axis=-2)  # (the first of equal minima)
+        chosen = np.take_along_axis(heldout_errors, best[..., None, :], axis=-2)[..., 0, :]
+        self.heldout_mean_ = chosen.mean(axis=-1)
+        self.heldout_sem_ = chosen.std(axis=-1, ddof=1) / np.sqrt(F) if F > 1 else np.full(chosen.shape[:-1], np.nan)
 
     def suggest_n_signatures_heldout(self, one_standard_error: bool = False):
         """The K of ``ns_signatures`` with the smallest ``heldout_mean_`` (the first of equal ones); with
         ``one_standard_error`` the smallest K whose mean is at most that minimum plus the minimum's ``heldout_sem_`` (the
-        customary rule; with a NaN standard error, at F = 1, the minimiser itself).  None before ``fit``."""
+        customary rule; with a NaN standard error, at F = 1, the minimiser itself).  None before ``fit``.  On a sweep with
+        ``lhalf_weights`` the K of ``suggest_penalty_heldout``'s pair."""
         if not self.n_splits:
             raise ValueError("'suggest_n_signatures_heldout' needs a sweep built with 'n_splits' > 0.")
         if not self._fitted:
             return None
+        if self.lhalf_weights:
+            return self.suggest_penalty_heldout(one_standard_error)[0]
         best = int(np.nanargmin(self.heldout_mean_))
         if not one_standard_error or np.isnan(self.heldout_sem_[best]):
             return self.ns_signatures[best]
         bound = self.heldout_mean_[best] + self.heldout_sem_[best]
         return min(k for k, mean in zip(self.ns_signatures, self.heldout_mean_) if mean <= bound)
+
+    def suggest_penalty_heldout(self, one_standard_error: bool = False):
+        """``(K, penalty)`` of the smallest ``heldout_mean_`` (the first of equal ones, K-major); with
+        ``one_standard_error``, among the cells whose mean is at most that minimum plus the minimum's ``heldout_sem_``, the
+        smallest K and then the largest penalty (the sparsest model the data cannot tell from the best; with a NaN standard
+        error, at F = 1, the minimiser itself).  None before ``fit``.
+
+        The penalty returned is the value fitted on TRAINING halves, which hold a fraction p = ``train_fraction`` of the
+        mutations.  The KL term scales with p and the l-half penalty with sqrt(p), so the same trade-off on the full
+        counts is ``penalty / sqrt(p)``."""
+        if not self.n_splits or not self.lhalf_weights:
+            raise ValueError("'suggest_penalty_heldout' needs a sweep built with 'lhalf_weights' and 'n_splits' > 0.")
+        if not self._fitted:
+            return None
+        mean, sem = np.asarray(self.heldout_mean_), np.asarray(self.heldout_sem_)
+        bk, bl = np.unravel_index(int(np.nanargmin(mean)), mean.shape)
+        if not one_standard_error or np.isnan(sem[bk, bl]):
+            return self.ns_signatures[bk], self.lhalf_weights[bl]
+        bound = mean[bk, bl] + sem[bk, bl]
+        cells = [(self.ns_signatures[i], self.lhalf_weights[j]) for i in range(mean.shape[0]) for j in range(mean.shape[1]) if mean[i, j] <= bound]
+        return min(cells, key=lambda c: (c[0], -c[1]))
 
     # ------------------------------------------------------------------ resamples and splits
     def _draw_datasets(self, batch, counts, slot_of, members) -> float:
@@ -293,7 +358,7 @@ class KLNMFSweep:
             fitting_kwargs: dict[str, Any] | None = None, history: bool = True) -> list[KLNMF]:
         type_checker("adata", adata, ANNDATA_TYPES)
         if fitting_kwargs and (set(fitting_kwargs) - {"weights_kl", "weights_lhalf"} or any(v is not None for v in fitting_kwargs.values())):
-            raise ValueError("A sweep has no weighted step: 'fitting_kwargs' (weights_kl, weights_lhalf) are not supported.")
+            raise ValueError("A sweep takes no 'fitting_kwargs': its weighted step is set up by the constructor ('weights_kl' for all members, 'lhalf_weights' as a penalty axis).")
         n_given = SignatureNMF._n_given(given_parameters)
         if given_parameters and "asignatures" in given_parameters:
             for k in self.ns_signatures:  # (KLNMF.fit's own check, before any member is touched)
@@ -301,8 +366,12 @@ class KLNMFSweep:
         n_obs, n_vars = np.shape(adata.X)
         R, F = self.n_resamples, self.n_splits
         counts = check_counts(adata.X) if R or F else None  # (before anything touches the device)
+        if self.weights_kl is not None:  # (a single fit's own check and exceptions, before any member is touched)
+            probe = self._model(self.ns_signatures[0])
+            probe.adata = adata
+            probe._weight_vector("weights_kl", self.weights_kl)
         members = self._members(init_kwargs)
-        in_reach = [n_obs <= MAX_SAMPLES and n_vars <= MAX_FEATURES and k <= MAX_SIGNATURES and k > n_given for k, _, _ in members]
+        in_reach = [n_obs <= MAX_SAMPLES and n_vars <= MAX_FEATURES and k <= MAX_SIGNATURES and k > n_given for k, _, _, _ in members]
 
         t0 = time.perf_counter()
         batch_ids = [i for i, ok in enumerate(in_reach) if ok]
@@ -324,18 +393,21 @@ class KLNMFSweep:
                 t_draw = self._draw_datasets(batch, counts, slot_of, members)
             # every member in order: initialised (batched) or fitted (fallback) exactly as the tutorial's loop would
             # do it, so that the legacy NumPy RNG of the random methods advances the same way
-            for i, (k, kwargs, r) in enumerate(members):
+            for i, (k, kwargs, r, l) in enumerate(members):
                 model = self._model(k)
+                fitting = self._fitting_kwargs(l)
                 ta = time.perf_counter()
                 if i in slot_of:
                     model._setup_adata(self._member_adata(adata, r))  # (the member's own copy, X clipped as fit() leaves it)
                     model._initialize(given_parameters, kwargs)
-                    model._setup_fitting_parameters(None)
+                    model._setup_fitting_parameters(fitting)
                     batch.upload_member(slot_of[i], model.asignatures.X, model.adata.obsm["exposures"])
+                    if model.weights_kl is not None or model.weights_lhalf is not None:
+                        batch.set_weights(slot_of[i], model.weights_kl, model.weights_lhalf)
                     self._close_engine(model)  # (a sweep holds no per-member engine)
                     t_init += time.perf_counter() - ta
                 else:
-                    model.fit(self._member_adata(adata, r), given_parameters, kwargs, history=history)
+                    model.fit(self._member_adata(adata, r), given_parameters, kwargs, fitting, history=history)
                     model.compute_reconstruction_errors()
                     self._close_engine(model)
                     t_fallback += time.perf_counter() - ta
@@ -376,10 +448,11 @@ class KLNMFSweep:
         self.models_ = models
         self.batched_ = np.array([i in slot_of for i in range(len(members))], dtype=bool)
         cols = max(1, len(self.seeds or []))
-        shape = (len(self.ns_signatures), cols, R or F) if R or F else (len(self.ns_signatures), cols)
+        shape = (len(self.ns_signatures),) + ((len(self.lhalf_weights),) if self.lhalf_weights else ()) + (cols,) + ((R or F,) if R or F else ())
         self.reconstruction_errors_ = np.array([m.reconstruction_error for m in models]).reshape(shape)
-        self.resample_of_ = np.array([-1 if F else r for _, _, r in members], dtype=int)
-        self.split_of_ = np.array([r if F else -1 for _, _, r in members], dtype=int)
+        self.resample_of_ = np.array([-1 if F else r for _, _, r, _ in members], dtype=int)
+        self.split_of_ = np.array([r if F else -1 for _, _, r, _ in members], dtype=int)
+        self.lhalf_of_ = np.array([l for _, _, _, l in members], dtype=int)
         if F:
             self.heldout_errors_ = np.array([float(np.sum(np.asarray(m.adata.obs["heldout_error"]))) for m in models]).reshape(shape)
             self._summarise_heldout(self.reconstruction_errors_, self.heldout_errors_)
