@@ -204,6 +204,9 @@ int salnmf_set_mv_queued(salnmf_engine* e, int on);
  * (global_load_lds_dwordx4, no registers) where n_features == 96 and W is 16-byte aligned; 0: through registers (the
  * form of rounds 1-4; any other layout takes it anyway).  Same results bit for bit (W is copied, not computed). */
 int salnmf_set_w_dma(salnmf_engine* e, int on);
+/* Workgroups of the update passes' launches: min(compute units, ceil(tiles / 4)), four waves each.  With it a caller can
+ * tell which form the leftover round of a shape takes (csrc/salnmf_fused_kernel.h: the pairing rule). */
+int salnmf_fused_grid(salnmf_engine* e, int* grid);
 int salnmf_mv_step_objective(salnmf_engine* e, int n_steps, int n_given, double lam, double delta,
                              double* gamma_inout, double* objective_out, int more_follows);
 /* only MvNMF._update_W (:190-195) / only _update_H (= salnmf_update_H) for the

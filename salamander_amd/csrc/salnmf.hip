@@ -146,6 +146,7 @@ struct salnmf_engine {
     hipStream_t stream3 = nullptr;  // MvNMF: read-back of the line-search scalars past a speculative pass on the main stream
     hipEvent_t evW = nullptr, evPrepW = nullptr, evTrial = nullptr, evLogdet = nullptr, evObj = nullptr;
     double* Halt = nullptr;      // [Np][KP] second H buffer: the speculative update_H pass of MvNMF; the state kept by salnmf_kl_step_keep (lazily allocated)
+    double* Hpp = nullptr;       // [Np][KP] third H buffer: where a joint step with a paired leftover round writes the new H (kl_step_once; lazily allocated)
     double* Wkeep = nullptr;     // [K][V] W of the state kept by salnmf_kl_step_keep (lazily allocated)
     double* Hkeep = nullptr;     // [Np][KP] H of the kept state of an engine with feature blocks (its steps use Halt themselves)
     double* Wdst = nullptr;      // where the next W tail writes its result (null = in place); set for one step by a kept block
@@ -351,8 +352,8 @@ static FusedParams fused_params(salnmf_engine* e) {
     p.ntiles = e->ntiles;
     p.wdma = e->w_dma ? 1 : 0;
 #ifdef SALNMF_DEV_PROFILE
-    if (!e->fk_prof && hipMalloc(&e->fk_prof, FK_PROF_ROWS * (FK_NSEC + 1) * sizeof(unsigned long long)) == hipSuccess)
-        (void)hipMemset(e->fk_prof, 0, FK_PROF_ROWS * (FK_NSEC + 1) * sizeof(unsigned long long));
+    if (!e->fk_prof && hipMalloc(&e->fk_prof, FK_PROF_ROWS * FK_PROF_COLS * sizeof(unsigned long long)) == hipSuccess)
+        (void)hipMemset(e->fk_prof, 0, FK_PROF_ROWS * FK_PROF_COLS * sizeof(unsigned long long));
     p.prof = e->fk_prof;
 #endif
     return p;
@@ -478,6 +479,24 @@ static int ensure_halt(salnmf_engine* e) {
     return 0;
 }
 
+// The paired leftover round of the joint step (salnmf_fused_kernel.h: the pairing rule) has one workgroup read a tile's old H
+// rows and another store its new ones, with nothing that orders the two: it runs only in a pass that does not update H in
+// place.  A step of a shape that pairs therefore writes the new H to a buffer of its own and the buffers change roles (the
+// kept state of salnmf_kl_step_keep and MvNMF's speculation live in Halt, which stays what it was).  Same traffic, same bits;
+// one more H-sized allocation, zeroed like Halt and for the same reason.
+static bool leftover_pairs(const salnmf_engine* e) {
+    if (e->NB > 1 || e->NC > 1) return false;
+    const int64_t nleft = e->ntiles % ((int64_t)e->grid * WAVES);
+    return nleft > 0 && 2 * nleft <= e->grid;
+}
+static int ensure_hpp(salnmf_engine* e) {
+    if (e->Hpp) return 0;
+    const size_t bytes = (size_t)e->Np * e->KP * sizeof(double);
+    HIPCK(hipMalloc(&e->Hpp, bytes));
+    HIPCK(hipMemsetAsync(e->Hpp, 0, bytes, e->stream));
+    return 0;
+}
+
 void salnmf::launch_xlogx_lane(const double* X, int64_t Np, int V, double* c, hipStream_t stream) {
     hipLaunchKernelGGL(xlogx_lane_kernel, dim3((unsigned)((Np + 15) / 16)), dim3(256), 0, stream, X, Np, V, VMAX, c);
 }
@@ -521,12 +540,19 @@ static int kl_step_once(salnmf_engine* e, int n_given, hipEvent_t* ev, bool keep
     } reset_wdst{e};
     FusedParams p = fused_params(e);
     const bool all_given = n_given >= e->K;  // _utils_klnmf.py:330-331: W untouched
+    // (a kept step writes another buffer anyway; with all signatures given the pass forms no numerator and has no cooperative tile)
+    const bool pingpong = !keep && !all_given && leftover_pairs(e);
+    if (pingpong) {
+        CK(ensure_hpp(e));
+        p.Hout = e->Hpp;
+    }
     if (obj_slot >= 0) {
         if (keep) {
             p.Hout = e->Halt;
             e->Wdst = e->Wkeep;
         }
         CK((launch_fused<true, true, true>(e, p)));
+        if (pingpong) std::swap(e->H, e->Hpp);
         e->h_pending = false;
         TailParams t = tail_params(e, e->grid, e->red, n_given, SALNMF_CLIP_ALL, 1, false);
         t.kl_part = e->KLpart;
@@ -554,6 +580,7 @@ static int kl_step_once(salnmf_engine* e, int n_given, hipEvent_t* ev, bool keep
     else
         CK((launch_fused<true, true, false>(e, p, 0, bound ? ev[0] : nullptr, bound ? ev[1] : nullptr)));
     e->h_pending = false;  // the pass wrote H in full
+    if (pingpong) std::swap(e->H, e->Hpp);
     if (ev && !bound) HIPCK(hipEventRecord(ev[1], e->stream));
     const bool tail_bound = ev && !all_given && !sharded(e);
     if (ev && !tail_bound) HIPCK(hipEventRecord(ev[2], e->stream));
@@ -614,14 +641,14 @@ void salnmf_destroy(salnmf_engine* e) {
     if (e->stream) (void)hipStreamSynchronize(e->stream);
 #ifdef SALNMF_DEV_PROFILE
     if (e->fk_prof) {  // section clocks of every fused pass this engine launched (salnmf_fused_kernel.h: FK_TICK)
-        std::vector<unsigned long long> rows(FK_PROF_ROWS * (FK_NSEC + 1));
+        std::vector<unsigned long long> rows(FK_PROF_ROWS * FK_PROF_COLS);
         unsigned long long t[FK_NSEC + 1] = {};
         size_t nw = 0;
         if (hipMemcpy(rows.data(), e->fk_prof, rows.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess) {
             for (size_t w = 0; w < FK_PROF_ROWS; ++w) {
-                if (rows[w * (FK_NSEC + 1) + FK_NSEC] == 0 && rows[w * (FK_NSEC + 1)] == 0) continue;
+                if (rows[w * FK_PROF_COLS + FK_NSEC] == 0 && rows[w * FK_PROF_COLS] == 0) continue;
                 ++nw;
-                for (int i = 0; i <= FK_NSEC; ++i) t[i] += rows[w * (FK_NSEC + 1) + i];
+                for (int i = 0; i <= FK_NSEC; ++i) t[i] += rows[w * FK_PROF_COLS + i];
             }
         }
         if (t[FK_NSEC] > 0) {
@@ -638,6 +665,20 @@ void salnmf_destroy(salnmf_engine* e) {
                     fprintf(stderr, "  %-24s %6.2f %%  %9.0f cycles per %s\n", names[i], 100.0 * t[i] / tot, (double)t[i] / (per_tile ? (double)t[FK_NSEC] : (double)nw),
                             per_tile ? "(wave, tile)" : "wave and launch x launches");
                 }
+            // the cooperative leftover tile's sections by role, as the kernel recorded them (salnmf_fused_kernel.h: FK_PROF_COLS)
+            static const char* roles[4] = {"", "both (one workgroup)", "G (numerator share)", "U (U product + H update)"};
+            for (unsigned long long role = 1; role <= 3; ++role) {
+                unsigned long long s[4] = {}, launches = 0;
+                for (size_t w = 0; w < FK_PROF_ROWS; ++w) {
+                    const unsigned long long* row = &rows[w * FK_PROF_COLS + FK_NSEC + 1];
+                    if (row[0] != role) continue;
+                    launches += row[1];
+                    for (int i = 0; i < 4; ++i) s[i] += row[2 + i];
+                }
+                if (launches)
+                    fprintf(stderr, "  cooperative tile, role %-24s load+stage %7.0f  phase_A %7.0f  wait_slowest_wave %7.0f  phase_B %7.0f  cycles per wave and launch (%llu wave launches)\n",
+                            roles[role], (double)s[0] / launches, (double)s[1] / launches, (double)s[2] / launches, (double)s[3] / launches, launches);
+            }
         }
         (void)hipFree(e->fk_prof);
     }
@@ -650,7 +691,7 @@ void salnmf_destroy(salnmf_engine* e) {
     if (e->H32) (void)hipFree(e->H32);
     if (e->p2p.abort_dev) (void)hipFree(e->p2p.abort_dev);
     double* bufs[] = {e->PR, e->wones, e->wzeros, e->Gblk, e->Uacc, e->xlx, e->X, e->H, e->W, e->wkl, e->wlh, e->Gpart, e->Hsumpart, e->KLpart, e->red,
-                      e->objpart, e->scal, e->Wunc, e->Wtrial, e->mvA, e->mvB, e->cs, e->scratch, e->Halt, e->KLpart2, e->Wkeep, e->Hkeep, e->objring,
+                      e->objpart, e->scal, e->Wunc, e->Wtrial, e->mvA, e->mvB, e->cs, e->scratch, e->Halt, e->Hpp, e->KLpart2, e->Wkeep, e->Hkeep, e->objring,
                       e->alpha, e->beta, e->Lemb, e->Uemb, e->aux, e->xrowsum, e->corrpart, e->gU, e->galpha, e->gaux, e->mvS};
     for (double* b : bufs)
         if (b) (void)hipFree(b);
@@ -1110,6 +1151,12 @@ int salnmf_set_lockstep(salnmf_engine* e, int on) {
 int salnmf_set_w_dma(salnmf_engine* e, int on) {
     if (!e) return fail("null engine");
     e->w_dma = on != 0;
+    return 0;
+}
+
+int salnmf_fused_grid(salnmf_engine* e, int* grid) {
+    if (!e || !grid) return fail("null argument");
+    *grid = e->grid;
     return 0;
 }
 

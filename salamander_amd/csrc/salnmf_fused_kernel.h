@@ -26,6 +26,12 @@ namespace salnmf {
 // the tile loop, so hipcc can count vmcnt exactly: with them it falls back to `s_waitcnt vmcnt(0)` at the
 // loop's back edge, which exposes the latency of the H stores of every tile (~1.1 k cycles per tile).
 //
+// Leftover round (the joint steps; tiles = rounds * waves of the grid + L): with L <= workgroups the L tiles are worked on by
+// whole workgroups (process_tile_coop), and with 2 L <= workgroups by TWO each -- workgroup b forms the tile's share of G
+// (role G, into the slab it has always landed in), workgroup b + ceil(grid / 2), otherwise idle, the tile's U and the H update
+// (role U).  Both form P and the ratio themselves; they exchange nothing and never wait for each other.  Same bits in every
+// form.  c2: 106 leftover tiles on 256 workgroups.
+//
 // PERSIST: p.nsteps joint update_WH steps in ONE launch (requires every workgroup of the grid to be resident: one
 // per CU, grid <= number of CUs).  The workgroups stay on their CUs; per step each publishes its numerator slab,
 // the workgroup that owns signature row k (the ones that run out of tiles first) waits for all slabs, runs the
@@ -53,11 +59,16 @@ namespace salnmf {
 // numerator half) 1 + 7 h + {0 stage H, 1 P product, 2 KL terms, 3 divisions, 4 prefetch issue + R transpose, 5 G phase,
 // 6 U phase + H update}; 15 epilogue.
 constexpr int FK_NSEC = 16;
+// a wave's row of the profile: the sections, its tile count, then -- written only by launches in which the wave's workgroup had
+// a cooperative leftover tile -- that tile's role (1 both, 2 G, 3 U), the number of such launches and sections 9 .. 12 of those
+// launches alone (the rows also collect passes without a cooperative tile, and MVJ passes use 9 .. 12 with another meaning)
+constexpr int FK_PROF_COLS = FK_NSEC + 1 + 6;
 template <int KS, int KTM, int KR, bool DO_G, bool DO_U, bool DO_STATS, bool WTS = false, bool PERSIST = false, bool BLOCKED = false, bool RGIVEN = false,
           bool MVJ = false>
 __global__ void __launch_bounds__(BLOCK, 1) fused_kernel(FusedParams p) {
 #ifdef SALNMF_DEV_PROFILE
     unsigned long long tks[FK_NSEC] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tk0 = __builtin_amdgcn_s_memtime(), tk1, ntl = 0;
+    int fk_role = 0;
     // (sched_barrier on both sides: the machine scheduler moves nothing across a boundary)
 #define FK_TICK(i) do { __builtin_amdgcn_sched_barrier(0); tk1 = __builtin_amdgcn_s_memtime(); tks[i] += tk1 - tk0; tk0 = tk1; __builtin_amdgcn_sched_barrier(0); } while (0)
 #else
@@ -168,6 +179,19 @@ __global__ void __launch_bounds__(BLOCK, 1) fused_kernel(FusedParams p) {
     const int64_t nleft = p.ntiles % tstride;
     const bool coop = COOP && nleft > 0 && nleft <= (int64_t)gridDim.x && p.hscale == nullptr;
     const int64_t nfull = coop ? p.ntiles - nleft : p.ntiles;  // tiles of the one-wave-per-tile rounds
+    // Paired form: with at most half as many leftover tiles as workgroups, workgroup b < L keeps the numerator share of
+    // tile nfull + b (role G: its slab is the one the tile's contribution has always landed in) and workgroup b + ceil(grid / 2),
+    // which would idle otherwise, takes the tile's U product and H update (role U).  The two exchange nothing: both form the
+    // tile's P and ratio from X, H and the old W.  The map depends on the shape alone.  (b + ceil(grid / 2), not grid - 1 - b:
+    // workgroups are dealt round-robin to the 8 XCDs, so on a grid that is a multiple of 16 the two workgroups of a pair share
+    // an L2 and the tile's X and H lines come from memory once.)  The persistent instantiation keeps the one-workgroup form.
+    // Only where the pass does NOT update H in place (p.Hout != p.H: the host hands the joint step a second buffer and swaps,
+    // salnmf.hip: kl_step_once): role G reads the tile's old rows from p.H and role U stores the new ones to p.Hout, and nothing
+    // orders the two workgroups.  With distinct buffers no workgroup of the launch writes what another reads, whatever their
+    // relative progress; an in-place launch takes the one-workgroup form, which loads, passes a barrier and then stores.
+    constexpr bool PAIR = COOP && !PERSIST;
+    const int64_t upart0 = (int64_t)gridDim.x - (int64_t)(gridDim.x / 2);  // first workgroup with role U
+    const bool paired = PAIR && coop && 2 * nleft <= (int64_t)gridDim.x && p.Hout != p.H;
 
     // lane's slice of an H tile: element pair e = 2*lane + 128*j of the contiguous [16][KP] block
     int hrow[HV], hcol[HV];
@@ -243,10 +267,10 @@ __global__ void __launch_bounds__(BLOCK, 1) fused_kernel(FusedParams p) {
     // the slot where the next tile's prefetch would go: wave 0 sends the H tile by DMA into its free H buffer, every wave
     // loads its own columns of X into the (free) X prefetch registers -- the cooperative tile then starts without a memory
     // round trip of its own (3.1 k cycles of its 12.6 k at c2, profiles/r05/epilogue.md)
-    const bool coop_here = COOP && HDMA && coop && (int64_t)blockIdx.x < nleft;  // (uniform)
+    const bool coop_here = COOP && HDMA && coop && ((int64_t)blockIdx.x < nleft || (paired && (int64_t)blockIdx.x >= upart0 && (int64_t)blockIdx.x - upart0 < nleft));  // (uniform)
     bool coop_fetched = false;
     auto coop_prefetch = [&]() __attribute__((always_inline)) {
-        const int64_t ct = nfull + blockIdx.x;
+        const int64_t ct = nfull + ((int64_t)blockIdx.x < nleft ? (int64_t)blockIdx.x : (int64_t)blockIdx.x - upart0);  // (role U: the partner's tile)
         const int wvu = __builtin_amdgcn_readfirstlane(wave);
         if (wvu == 0) load_tile_H(ct);  // -> buffer (tiles per wave) & 1 of wave 0's region
         const int vt0 = wvu < 2 ? 2 * wvu : wvu + 2, nvt = wvu < 2 ? 2 : 1;  // the feature tiles of this wave: {0,1} {2,3} {4} {5}
@@ -645,7 +669,13 @@ __global__ void __launch_bounds__(BLOCK, 1) fused_kernel(FusedParams p) {
     //            (one lane per (sample, column), sequential dot product over the features)
     // Per entry the arithmetic is the reference's; what differs from process_tile is only which wave's accumulator a
     // contribution to G lands in and the summation order of the remainder columns of U (rounding level).
-    auto process_tile_coop = [&](int64_t ctile) __attribute__((always_inline)) {
+    // Roles (paired form, see the pairing rule above): ROLE 0 is all of the above in one workgroup; ROLE 1 (G) is phase A without
+    // the store of R -- no barrier behind it, no phase B; ROLE 2 (U) is phase A's P chain and division with the store of R, the
+    // barrier and phase B -- no G MFMAs, no park, no KL terms (the objective counts the tile once, in role G).  Each chain is
+    // the one of ROLE 0, so the slab and the H rows have the same bits whichever form runs.
+    auto process_tile_coop = [&](int64_t ctile, auto roletag) __attribute__((always_inline)) {
+        constexpr int ROLE = decltype(roletag)::value;
+        constexpr bool RG = ROLE != 2, RU = ROLE != 1;
         const int64_t n0 = ctile * 16;
         // (indices derived from an opaque copy of the thread index: nothing of this once-per-launch section may be
         // hoisted above the tile loop, where it would cost registers)
@@ -714,7 +744,7 @@ __global__ void __launch_bounds__(BLOCK, 1) fused_kernel(FusedParams p) {
             const double* wb = Wl + q * WS + 16 * VTI + c16;
 #pragma unroll
             for (int s2 = 0; s2 < KS; ++s2) pp = mfma(ha[4 * s2], wb[4 * s2 * WS], pp);
-            if (DO_STATS) {
+            if (DO_STATS && RG) {
                 // this feature tile's share of the unweighted KL partial (tile_kl's masked form, four entries per lane)
                 bool valid[4], ok = true;
 #pragma unroll
@@ -745,8 +775,9 @@ __global__ void __launch_bounds__(BLOCK, 1) fused_kernel(FusedParams p) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 pp[r] = div_path(xv[r], pp[r]);
-                Rs[(q + 4 * r) * RS + 16 * VTI + c16] = pp[r];
+                if (RU) Rs[(q + 4 * r) * RS + 16 * VTI + c16] = pp[r];
             }
+            if constexpr (RG) {
             // this tile's contribution to G is parked in LDS (accumulator layout, indexed like the epilogue's tiles); the
             // epilogue's owner waves pick it up before they reuse LDS and add it after the four waves' accumulators.  The
             // accumulators themselves are not touched outside the tile loop (doing so changes hipcc's register assignment
@@ -780,6 +811,7 @@ __global__ void __launch_bounds__(BLOCK, 1) fused_kernel(FusedParams p) {
                     if (q == 0) cslab[CO_::COOP_REM + j * VMAX + 16 * VTI + c16] = t;
                 }
             }
+            }  // RG
         };
         {
             using std::integral_constant;
@@ -788,9 +820,10 @@ __global__ void __launch_bounds__(BLOCK, 1) fused_kernel(FusedParams p) {
             else if (wv == 2) phase_a(integral_constant<int, 4>{}, xx[0]);
             else phase_a(integral_constant<int, 5>{}, xx[0]);
         }
-        __syncthreads();  // the ratio tile is complete
-        FK_TICK(10);  // phase A + its barrier
+        if (RU) __syncthreads();  // the ratio tile is complete
+        FK_TICK(10);  // phase A + its barrier (role G: no barrier)
         // ---- phase B
+        if constexpr (RU) {
         if (wv < KT) {
             const int kt = wv;
             d4 u = (d4){0, 0, 0, 0};
@@ -819,6 +852,7 @@ __global__ void __launch_bounds__(BLOCK, 1) fused_kernel(FusedParams p) {
                 p.Hout[(n0 + n) * KP + KB + j] = clip_lo(hn, WTS && wlh ? kEps : p.hfloor);
             }
         }
+        }  // RU
     };
 
     tile = (int64_t)blockIdx.x * WAVES + wave;
@@ -879,7 +913,19 @@ __global__ void __launch_bounds__(BLOCK, 1) fused_kernel(FusedParams p) {
         }
     }
     FK_TICK(8);  // (non-MVJ kernels: sections 8..12 time the cooperative tile -- 8 is always ~0: the loop's own ticks precede it)
-    if (COOP && coop && (int64_t)blockIdx.x < nleft) process_tile_coop(nfull + blockIdx.x);
+    if (COOP && coop) {
+        using std::integral_constant;
+        const int64_t b = blockIdx.x;
+        if (PAIR && paired) {
+            if (b < nleft) process_tile_coop(nfull + b, integral_constant<int, 1>{});
+            else if (b >= upart0 && b - upart0 < nleft) process_tile_coop(nfull + (b - upart0), integral_constant<int, 2>{});
+        } else if (b < nleft) {
+            process_tile_coop(nfull + b, integral_constant<int, 0>{});
+        }
+#ifdef SALNMF_DEV_PROFILE
+        fk_role = (PAIR && paired) ? (b < nleft ? 2 : (b >= upart0 && b - upart0 < nleft ? 3 : 0)) : (b < nleft ? 1 : 0);
+#endif
+    }
     FK_TICK(12);
 
     // ---- workgroup reductions, fixed order (deterministic)
@@ -1070,9 +1116,14 @@ __global__ void __launch_bounds__(BLOCK, 1) fused_kernel(FusedParams p) {
     FK_TICK(15);
 #ifdef SALNMF_DEV_PROFILE
     if (p.prof != nullptr && (threadIdx.x & 63) == 0) {  // (one row per wave of the grid: no atomics, launches are serialised)
-        unsigned long long* row = p.prof + ((size_t)blockIdx.x * WAVES + (threadIdx.x >> 6)) * (FK_NSEC + 1);
+        unsigned long long* row = p.prof + ((size_t)blockIdx.x * WAVES + (threadIdx.x >> 6)) * FK_PROF_COLS;
         for (int i = 0; i < FK_NSEC; ++i) row[i] += tks[i];
         row[FK_NSEC] += ntl;
+        if (fk_role != 0) {
+            row[FK_NSEC + 1] = (unsigned long long)fk_role;
+            row[FK_NSEC + 2] += 1;
+            for (int i = 0; i < 4; ++i) row[FK_NSEC + 3 + i] += tks[9 + i];
+        }
     }
 #endif
 #undef FK_TICK

@@ -154,7 +154,7 @@ struct FusedParams {
     int K;
     int64_t ntiles;
     int wdma;               // W -> LDS by LDS-DMA where the layout allows it (stage_W_dma_issue); 0: through registers (stage_W)
-    // development builds (SALNMF_DEV_PROFILE): [waves of the grid][FK_NSEC + 1] shader-clock cycles per section of the pass
+    // development builds (SALNMF_DEV_PROFILE): [waves of the grid][FK_PROF_COLS] shader-clock cycles per section of the pass
     // summed over the launches (+ the wave's number of tiles), or null -- printed by salnmf_destroy (profiles/r05/mvj_sections.md)
     unsigned long long* prof;
     // feature blocks (n_features > 96; fused_kernel<..., BLOCKED>, update_H pass only): U = R W^T is a sum over the

@@ -131,6 +131,12 @@ class Engine:
         """W into the workgroups' LDS by LDS-DMA (default) or through registers (``include/salnmf.h: salnmf_set_w_dma``)."""
         _lib.check(self._lib.salnmf_set_w_dma(self._h, int(bool(on))))
 
+    def fused_grid(self) -> int:
+        """Workgroups of the update passes' launches (``include/salnmf.h: salnmf_fused_grid``)."""
+        g = ctypes.c_int(0)
+        _lib.check(self._lib.salnmf_fused_grid(self._h, ctypes.byref(g)))
+        return int(g.value)
+
     def set_mv_queued(self, on: bool = True):
         """MvNMF steps queued ahead of the host with the line-search decision on the device (default) or the classic form
         (``include/salnmf.h: salnmf_set_mv_queued``)."""

@@ -1,5 +1,7 @@
 """Section clocks of the fused passes (a SALNMF_DEV_PROFILE build: tools/build_variant.sh p -DSALNMF_DEV_PROFILE, run with
-SALNMF_LIB=salamander_amd/lib/libsalnmf_p.so): one engine per workload, the table is printed when the engine closes."""
+SALNMF_LIB=salamander_amd/lib/libsalnmf_p.so): one engine per workload, the table is printed when the engine closes.  Where the shape has a cooperative leftover round the
+table ends with that tile's sections (9-12) averaged over the workgroups of each role separately: G and U in the paired
+form, "both" in the one-workgroup form (csrc/salnmf_fused_kernel.h: the pairing rule)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
