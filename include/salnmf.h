@@ -902,6 +902,26 @@ int salnmf_signature_change(int device, const double* counts_a, int64_t n_sample
                             double* tied_exposures_a, double* tied_exposures_b, double* errors, int* n_iterations, int* converged,
                             double* null_statistics, int* null_n_iterations, double* draws, double* timings);
 
+/* ---- Refit of exposures to FIXED signatures under a NEGATIVE-BINOMIAL likelihood: counts overdispersed around h W with variance
+ * p + p^2 / alpha (csrc/salnmf_nb.h).  counts, signatures, the problems (dataset -1 the counts, dataset r
+ * resample r of salnmf_resample_counts(counts, n_resamples, seed)), the iteration arguments, the quantiles, chunk_bytes, every
+ * output and timings as salnmf_refit_exposures.  dispersion  n_samples: sample n's alpha, which its resamples carry too.
+ *   x = max(row, SALNMF_EPSILON);  h_k = (sum_v x_v) / n_signatures;
+ *   step (update_H, _utils_klnmf.py:258-264, with the negative binomial's second product): p = h W, a_v = x_v / p_v,
+ *   b_v = (x_v + alpha) / (p_v + alpha), h_k <- max((h_k sum_v W[k, v] a_v) / (sum_v W[k, v] b_v), SALNMF_EPSILON);
+ *   objective: sum_v [ x_v log(x_v / p_v) - (x_v + alpha) log((x_v + alpha) / (p_v + alpha)) ] -- not negative, 0 at p = x, the KL
+ *   divergence as alpha -> infinity -- at iteration 0 and every multiple of conv_test_freq; stop rule, latching, converged and
+ *   n_iterations as salnmf_refit_exposures.  errors and errors_resampled hold this divergence.
+ * Refused on the host before any launch, status 1 and salnmf_last_error: what salnmf_refit_exposures refuses, a null dispersion,
+ * and a dispersion that is not finite or lies outside (0, 1e6] (towards infinity the second logarithm's argument is 1 to
+ * rounding; salnmf_refit_exposures is the limit). */
+int salnmf_nb_refit_exposures(int device, const double* counts, int64_t n_samples, int n_features, const double* signatures,
+                              int n_signatures, const double* dispersion, int n_resamples, uint64_t seed, int n_quantiles,
+                              const double* quantiles, int min_iterations, int max_iterations, int conv_test_freq, double tol,
+                              int64_t chunk_bytes, double* exposures, double* errors, int* n_iterations, int* converged,
+                              double* exposures_quantiles, double* exposures_mean, int* n_iterations_resampled,
+                              double* errors_resampled, double* exposures_resampled, double* timings);
+
 #ifdef __cplusplus
 }
 #endif

@@ -166,6 +166,9 @@ SIGNATURES = {
     # which signature's share has changed between two samples, per pair of rows and tested signature: salamander_amd/sigchange.py
     "salnmf_signature_change": (c_int, [c_int, _D, c_int64, c_int, _D, c_int64, c_int, _D, c_int, _I, c_int, POINTER(c_uint8), c_int, c_uint64, c_int,
                                         c_int, c_int, c_double, c_int64, POINTER(c_uint8), _D, _I, _D, _D, _D, _D, _D, _D, _I, _I, _D, _I, _D, _D]),
+    # refit to fixed signatures under a negative-binomial likelihood, per-sample dispersion: salamander_amd/nb.py
+    "salnmf_nb_refit_exposures": (c_int, [c_int, _D, c_int64, c_int, _D, c_int, _D, c_int, c_uint64, c_int, _D, c_int, c_int, c_int, c_double, c_int64,
+                                          _D, _D, _I, _I, _D, _D, _I, _D, _D, _D]),
 }
 
 OBJECTIVE_SLOTS = 256  # SALNMF_OBJECTIVE_SLOTS
