@@ -922,6 +922,36 @@ int salnmf_nb_refit_exposures(int device, const double* counts, int64_t n_sample
                               double* exposures_quantiles, double* exposures_mean, int* n_iterations_resampled,
                               double* errors_resampled, double* exposures_resampled, double* timings);
 
+/* ---- Draws from a FITTED negative-binomial model and the goodness-of-fit test they calibrate (csrc/salnmf_nbdraw.h, DESIGN.md
+ * section 24).  out  n_draws x n_samples x n_features: row n of draw b is one gamma-Poisson draw around exposures[n, :] @ signatures
+ * with dispersion[n] -- unconditional, the row total varies -- bit for bit by the contract of section 24:
+ *   P_v = sum_k h_k W[k, v] (ascending k, product then sum, no fused multiply-add);  lambda_v = g_v (P_v / alpha), g_v ~ Gamma(alpha, 1)
+ *   by Marsaglia-Tsang with a polar normal;  Lambda = sum_v lambda_v (ascending v);  T ~ Poisson(Lambda) by counted exponentials
+ *   below 10 and Hoermann's PTRS from 10 on;  T trials over the 40-bit table of lambda_v / Lambda as salnmf_draw_model_counts places
+ *   them.  Philox4x32-10, key = (seed & 0xffffffff, seed >> 32), counter (q, 0x4E420000 + stream, n, b).  Draw b does not depend on
+ *   n_draws.  signatures as given (rows of sum one expected, not normalised here).
+ * n_failed  one int: rows written as zeros because 64 gamma attempts, 128 exponentials or 64 PTRS attempts were all rejected (each
+ *   below 2^-100) or because Lambda reached 2^31; the status is 0 all the same, and a caller treats n_failed != 0 as an error.
+ * Refused on the host before any launch, status 1 and salnmf_last_error: a null argument; n_samples outside [1, 2^31); n_features
+ * or n_signatures outside [1, 96]; n_draws outside [1, 65536]; exposures or signature entries that are not finite or are negative;
+ * a row with sum_v P_v above 2^24; a dispersion that is not finite or lies outside (0, 1e6]. */
+int salnmf_draw_nb_counts(int device, const double* exposures, int64_t n_samples, int n_signatures, const double* signatures,
+                          int n_features, const double* dispersion, int n_draws, uint64_t seed, double* out, int* n_failed);
+
+/* The parametric-bootstrap test of section 16 under the negative-binomial model.  The observed fit is salnmf_nb_refit_exposures
+ * (n_resamples = 0) bit for bit; draw b is salnmf_draw_nb_counts of those exposures, read where the refit left them on the device,
+ * with the samples' own dispersions, written as max(count, SALNMF_EPSILON); its refit is salnmf_nb_refit_exposures of the draw with
+ * the same dispersions and iteration arguments; n_exceed[n] counts null_errors[b, n] >= errors[n] (false for a NaN) and null_mean[n]
+ * is their sum in ascending b over n_draws.  null_errors, null_n_iterations  n_draws x n_samples.  draws  n_draws x n_samples x
+ * n_features or null.  timings  4 doubles or null: device-event ms of the draw launches, the refit launches and the reduction, and
+ * the chunk count.  n_failed as above.  Refused: what salnmf_nb_refit_exposures refuses, n_draws outside [1, 65536], counts that are
+ * not integers, and a row total above 2^24. */
+int salnmf_nb_goodness_of_fit(int device, const double* counts, int64_t n_samples, int n_features, const double* signatures,
+                              int n_signatures, const double* dispersion, int n_draws, uint64_t seed, int min_iterations,
+                              int max_iterations, int conv_test_freq, double tol, int64_t chunk_bytes, double* exposures,
+                              double* errors, int* n_iterations, int* converged, int* n_exceed, double* null_mean,
+                              double* null_errors, int* null_n_iterations, double* draws, double* timings, int* n_failed);
+
 #ifdef __cplusplus
 }
 #endif

@@ -169,6 +169,10 @@ SIGNATURES = {
     # refit to fixed signatures under a negative-binomial likelihood, per-sample dispersion: salamander_amd/nb.py
     "salnmf_nb_refit_exposures": (c_int, [c_int, _D, c_int64, c_int, _D, c_int, _D, c_int, c_uint64, c_int, _D, c_int, c_int, c_int, c_double, c_int64,
                                           _D, _D, _I, _I, _D, _D, _I, _D, _D, _D]),
+    # draws from the fitted negative-binomial model and the goodness-of-fit test on them: salamander_amd/nb.py
+    "salnmf_draw_nb_counts": (c_int, [c_int, _D, c_int64, c_int, _D, c_int, _D, c_int, c_uint64, _D, _I]),
+    "salnmf_nb_goodness_of_fit": (c_int, [c_int, _D, c_int64, c_int, _D, c_int, _D, c_int, c_uint64, c_int, c_int, c_int, c_double, c_int64,
+                                          _D, _D, _I, _I, _I, _D, _D, _I, _D, _D, _I]),
 }
 
 OBJECTIVE_SLOTS = 256  # SALNMF_OBJECTIVE_SLOTS

@@ -13,6 +13,8 @@
 #include "salnmf_split.h"
 #define SALNMF_GOF_KERNELS 1
 #include "salnmf_gof.h"
+#define SALNMF_NBDRAW_KERNELS 1
+#include "salnmf_nbdraw.h"
 #include "salnmf_presence.h"
 #include "salnmf_change.h"
 #include "salnmf_sigchange.h"
@@ -331,6 +333,16 @@ void salnmf::gof_launch_model_draw(const double* H, const double* W, const uint3
 
 void salnmf::gof_launch_reduce(const GofReduceArgs& a, hipStream_t stream) {
     hipLaunchKernelGGL(gof_reduce_kernel, dim3((unsigned)((a.N + 255) / 256)), dim3(256), 0, stream, a);
+}
+
+// the negative-binomial model draw (salnmf_nbdraw.h), as salnmf_nb.hip uses it: one workgroup per (row, draw)
+void salnmf::nb_launch_draw(const double* H, const double* W, const double* alpha, const double* gd, const double* gc, double* out, unsigned* failed, int64_t N,
+                            int V, int K, uint64_t seed, double floor, int first, int count, hipStream_t stream) {
+    for (int done = 0; done < count; done += GOF_GRID_Y) {
+        const int now = std::min(GOF_GRID_Y, count - done);
+        const NbDrawArgs a{H, W, alpha, gd, gc, out + (size_t)done * N * V, failed, N, V, K, (uint32_t)seed, (uint32_t)(seed >> 32), floor, (uint32_t)(first + done)};
+        hipLaunchKernelGGL(nb_draw_kernel, dim3((unsigned)N, (unsigned)now), dim3(RESAMPLE_BLOCK), 0, stream, a);
+    }
 }
 
 // the presence test's draw (salnmf_presence.h): the same body, one workgroup per (pair, draw)

@@ -7,7 +7,10 @@ a hypermutated sample dictate its exposures.  :func:`nb_refit_exposures` fits th
 ``p + p**2 / alpha``, Poisson as ``alpha -> inf`` -- by the majorise-minimise step of the same shape (Gouvert et al. 2020;
 Pelizzola et al. 2023), every sample iterated and stopped on its own, with a dispersion per sample.
 :func:`estimate_dispersion` profiles the likelihood over a grid of ``alpha`` and says which value to pass, and whether the
-negative binomial is needed at all.  There is no CPU fallback.
+negative binomial is needed at all.  :func:`draw_nb_counts` draws count vectors from a fitted negative-binomial model on the
+device (``csrc/salnmf_nbdraw.h``), :func:`nb_goodness_of_fit` is the parametric-bootstrap test of
+:func:`goodness_of_fit <salamander_amd.gof.goodness_of_fit>` under that model, and :func:`dispersion_test` calibrates the
+dispersion estimate: a p-value for ``lr_statistic`` and an interval for the estimate.  There is no CPU fallback.
 """
 
 from __future__ import annotations
@@ -20,10 +23,13 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from .refit import RefitResult, check_arguments, refit_exposures
+from .gof import check_integer_counts, check_n_draws, draw_model_counts
+from .refit import RefitResult, check_arguments, normalize_signatures, refit_exposures
+from .resample import check_seed
 
 EPSILON = float(np.finfo(np.float32).eps)
 MAX_DISPERSION = 1e6  # towards infinity the second logarithm's argument is 1 to rounding; refit_exposures is the limit
+MAX_DRAW_MEAN = 2.0**24  # a model row's sum: the drawn total must stay far below 2**31
 
 
 @dataclass
@@ -172,9 +178,9 @@ def estimate_dispersion(counts, signatures, grid=np.geomspace(1, 1e4, 17), per_s
     ``poisson_log_likelihood = -KL + sum_v [x log x - x - lgamma(x + 1)]``; ``lr_statistic = 2 (l_NB(dispersion) - l_Poisson)``.
     ``grid`` must be strictly increasing with values in (0, 1e6].
 
-    **No p-value is returned.**  ``alpha = inf`` lies on the boundary of the parameter space and the exposures are fitted too;
-    calibrating ``lr_statistic`` needs draws from the fitted negative-binomial model (a gamma-Poisson generator on the device),
-    which the library does not have yet.
+    **No p-value is returned here.**  ``alpha = inf`` lies on the boundary of the parameter space and the exposures are fitted
+    too, so ``lr_statistic`` has no textbook null law.  Its null is the Poisson model, though, whose draws
+    (``draw_model_counts``) the library has: :func:`dispersion_test` drives this estimate over them and returns the p-value.
 
     **Bias.**  With many free exposures the maximum-likelihood ``alpha`` is pushed upward: the exposures absorb part of the
     overdispersion.  Gamma-Poisson data drawn with ``alpha = 20``, N = 40, gave in a CPU prototype
@@ -206,3 +212,210 @@ def estimate_dispersion(counts, signatures, grid=np.geomspace(1, 1e4, 17), per_s
     return DispersionResult(grid=g, profile=profile, dispersion=dispersion, at_upper_edge=edge, poisson_log_likelihood=poisson_ll, lr_statistic=lr,
                             exposures=H.reshape(A, N, K), divergence=divergence, n_iterations=nit.reshape(A, N), converged=conv.reshape(A, N).astype(bool),
                             timings=timings)
+
+
+@dataclass
+class NBGofResult:
+    exposures: np.ndarray  # (N, K): the observed negative-binomial refit, as nb_refit_exposures returns it
+    reconstruction_errors: np.ndarray  # (N,): its negative-binomial divergences
+    n_iterations: np.ndarray  # (N,) int32
+    converged: np.ndarray  # (N,) bool
+    dispersion: np.ndarray  # (N,)
+    log_likelihood: np.ndarray  # (N,): -divergence + nb_constant(counts, dispersion)
+    n_exceed: np.ndarray  # (N,) int32: draws b with null_errors[b, n] >= reconstruction_errors[n]
+    p_value: np.ndarray  # (N,): (1 + n_exceed) / (B + 1)
+    null_mean: np.ndarray  # (N,): the sum of null_errors[:, n] in ascending b, divided by B
+    null_errors: np.ndarray  # (B, N)
+    null_n_iterations: np.ndarray  # (B, N) int32
+    draws: np.ndarray | None = None  # (B, N, V) with keep_draws
+    timings: dict = field(default_factory=dict)
+
+
+@dataclass
+class DispersionTestResult:
+    estimate: DispersionResult  # estimate_dispersion of the counts
+    dispersion: np.ndarray | float  # = estimate.dispersion
+    at_upper_edge: np.ndarray | bool
+    lr_statistic: np.ndarray | float
+    p_value: np.ndarray | float  # (1 + #{null_lr >= lr_statistic}) / (B + 1) under the Poisson null
+    null_lr: np.ndarray  # (B,), or (B, N) with per_sample
+    dispersion_draws: np.ndarray | None = None  # (B,), or (B, N): the estimate on cohorts drawn from the NB fit at `dispersion`
+    dispersion_interval: np.ndarray | None = None  # (Q,) or (Q, N): order statistics of dispersion_draws, taken outward
+    dispersion_bias: np.ndarray | float | None = None  # median(dispersion_draws) / dispersion
+    quantiles: tuple = ()
+    timings: dict = field(default_factory=dict)
+
+
+def _failed_rows(n_failed: int, what: str) -> None:
+    if n_failed:
+        raise RuntimeError(f"salnmf: {what}: {n_failed} drawn rows ran out of attempts or reached a total of 2**31 and were written as zeros.")
+
+
+def draw_nb_counts(exposures, signatures, dispersion, n_draws: int, seed: int = 0, device: int = 0) -> np.ndarray:
+    """``n_draws`` count matrices drawn from the negative-binomial model around ``exposures (N, K) @ signatures (K, V)``:
+    ``(n_draws, N, V)`` float64 of integer values, entry (n, v) of every draw a gamma-Poisson count of mean ``P[n, v]`` and
+    variance ``P + P**2 / dispersion[n]`` (the contract: DESIGN.md section 24).  The draw is unconditional -- row totals
+    vary, unlike ``draw_model_counts`` -- because the negative-binomial refit leaves the scale free.  The signature rows are
+    divided by their sums; the exposures are finite and non-negative with row sums of at most 2**24; ``dispersion`` is a scalar
+    or one value per row, in (0, 1e6].  The same bits on every run, and draw b does not depend on ``n_draws``."""
+    S = normalize_signatures(signatures)
+    K, V = S.shape
+    H = np.ascontiguousarray(exposures, dtype=np.float64)
+    if H.ndim != 2 or H.shape[0] < 1 or H.shape[1] != K:
+        raise ValueError(f"'exposures' must be a matrix (samples x {K} signatures) with at least one row.")
+    if not np.isfinite(H).all() or (H < 0).any():
+        raise ValueError("Exposures must be finite and non-negative.")
+    N = H.shape[0]
+    alpha = check_dispersion(dispersion, N)
+    rows = np.flatnonzero(~((H @ S).sum(axis=1) <= MAX_DRAW_MEAN))
+    if rows.size:
+        raise ValueError(f"draw_nb_counts needs model row sums of at most 2**24: row {int(rows[0])} sums to {(H[int(rows[0])] @ S).sum():g}.")
+    B, seed = check_n_draws(n_draws), check_seed(seed)
+    lib = _lib.load_with_device()
+    out = np.empty((B, N, V), dtype=np.float64)
+    failed = np.zeros(1, dtype=np.int32)
+    p = _lib.pointer
+    _lib.check(lib.salnmf_draw_nb_counts(int(device), p(H), N, K, p(S), V, p(alpha), B, seed, p(out), p(failed)))
+    _failed_rows(int(failed[0]), "draw_nb_counts")
+    return out
+
+
+def nb_goodness_of_fit(counts, signatures, dispersion, n_draws: int = 200, seed: int = 0, keep_draws: bool = False, min_iterations: int = 500,
+                       max_iterations: int = 10000, conv_test_freq: int = 10, tol: float = 1e-7, chunk_bytes: int | None = None,
+                       device: int = 0) -> NBGofResult:
+    """The parametric-bootstrap test of every row of ``counts (N, V)`` against the fixed ``signatures (K, V)`` under the
+    negative-binomial model with ``dispersion`` (a scalar or one value per sample, in (0, 1e6]).
+
+    The observed fit is ``nb_refit_exposures(counts, signatures, dispersion, ...)`` bit for bit.  Draw b is
+    ``draw_nb_counts(exposures, signatures, dispersion, n_draws, seed)[b]`` and its refit
+    ``nb_refit_exposures(draws[b], signatures, dispersion, ...)``, bit for bit, with the same iteration arguments: the data and
+    the null go through one procedure.  ``p_value`` is ``(1 + n_exceed) / (n_draws + 1)``: small where the catalogue does not
+    explain the sample even with the variance ``p + p**2 / dispersion``.  Unlike ``goodness_of_fit`` the null vectors are not
+    conditional on the sample's total: the negative-binomial refit leaves the scale free, and the model's law of the total is
+    part of what is tested.  The counts are non-negative integers with row totals of at most 2**24; anything out of range is a
+    ``ValueError`` before the device is touched."""
+    t_start = time.perf_counter()
+    X, S, _, seed, min_it, max_it, freq, tol, _, chunk = check_arguments(counts, signatures, 0, seed, (), min_iterations, max_iterations,
+                                                                        conv_test_freq, tol, chunk_bytes)
+    check_integer_counts(X)
+    rows = np.flatnonzero(X.sum(axis=1) > MAX_DRAW_MEAN)
+    if rows.size:
+        raise ValueError(f"nb_goodness_of_fit needs row totals of at most 2**24: row {int(rows[0])} sums to {X[int(rows[0])].sum():.0f}.")
+    alpha = check_dispersion(dispersion, X.shape[0])
+    B = check_n_draws(n_draws)
+    (N, V), K = X.shape, S.shape[0]
+    lib = _lib.load_with_device()
+
+    H = np.empty((N, K), dtype=np.float64)
+    err = np.empty(N, dtype=np.float64)
+    nit = np.empty(N, dtype=np.int32)
+    conv = np.empty(N, dtype=np.int32)
+    exceed = np.empty(N, dtype=np.int32)
+    mean = np.empty(N, dtype=np.float64)
+    err_b = np.empty((B, N), dtype=np.float64)
+    nit_b = np.empty((B, N), dtype=np.int32)
+    drawn = np.empty((B, N, V), dtype=np.float64) if keep_draws else None
+    failed = np.zeros(1, dtype=np.int32)
+    ms = (c_double * 4)()
+    p = _lib.pointer
+    _lib.check(lib.salnmf_nb_goodness_of_fit(
+        int(device), p(X), N, V, p(S), K, p(alpha), B, seed, min_it, max_it, freq, tol, chunk,
+        p(H), p(err), p(nit), p(conv), p(exceed), p(mean), p(err_b), p(nit_b), p(drawn), ctypes.cast(ms, _lib._D), p(failed),
+    ))
+    _failed_rows(int(failed[0]), "nb_goodness_of_fit")
+    timings = {"draw_s": ms[0] / 1e3, "refit_s": ms[1] / 1e3, "reduce_s": ms[2] / 1e3, "refit_kernel_ms": ms[1], "n_chunks": int(ms[3]),
+               "total_s": time.perf_counter() - t_start}
+    return NBGofResult(exposures=H, reconstruction_errors=err, n_iterations=nit, converged=conv.astype(bool), dispersion=alpha,
+                       log_likelihood=-err + nb_constant(X, alpha), n_exceed=exceed, p_value=(1 + exceed.astype(np.int64)) / (B + 1), null_mean=mean,
+                       null_errors=err_b, null_n_iterations=nit_b, draws=drawn, timings=timings)
+
+
+def _cohort_profiles(cohorts, S, g, poisson: bool, it, device):
+    """``(profile (C, A, N), poisson log-likelihood (C, N) or None)`` of C cohorts ``(C, N, V)``: every cohort's A x N problem list,
+    one after the other, in ONE negative-binomial launch, and one Poisson refit of the C N rows."""
+    C, N, V = cohorts.shape
+    A = g.size
+    q = np.empty(0)
+    rows = np.ascontiguousarray(np.tile(cohorts[:, None], (1, A, 1, 1)).reshape(C * A * N, V))  # problem (c, a, n): sample n of cohort c at grid[a]
+    _, err, *_ = _call(rows, S, np.tile(np.repeat(g, N), C), 0, 0, q, *it, 0, False, device)
+    divergence = err.reshape(C, A, N)
+    profile = np.stack([[-divergence[c, a] + nb_constant(cohorts[c], np.full(N, g[a])) for a in range(A)] for c in range(C)])
+    if not poisson:
+        return profile, None
+    flat = np.ascontiguousarray(cohorts.reshape(C * N, V))
+    fit = refit_exposures(flat, S, min_iterations=it[0], max_iterations=it[1], conv_test_freq=it[2], tol=it[3], device=device)
+    return profile, (-fit.reconstruction_errors + poisson_constant(flat)).reshape(C, N)
+
+
+def dispersion_test(counts, signatures, grid=np.geomspace(1, 1e4, 17), n_draws: int = 200, seed: int = 0, interval: bool = True,
+                    quantiles=(0.025, 0.5, 0.975), per_sample: bool = False, min_iterations: int = 500, max_iterations: int = 10000,
+                    conv_test_freq: int = 10, tol: float = 1e-7, chunk_bytes: int | None = None, device: int = 0) -> DispersionTestResult:
+    """:func:`estimate_dispersion` with its two calibrations: is ``lr_statistic`` large, and how sure and how biased is the estimate?
+
+    **p_value.**  The null of ``lr_statistic`` is ``alpha = inf``, the Poisson model.  ``n_draws`` cohorts are drawn from the
+    Poisson fit (``draw_model_counts`` of ``refit_exposures``' exposures and the samples' totals), each goes through the same
+    A x N problem list and one Poisson refit, and ``p_value = (1 + #{null_lr >= lr_statistic}) / (n_draws + 1)``, for the cohort
+    or, with ``per_sample``, per sample.  The procedure applied to the data is applied to the null, so the boundary and the
+    fitted exposures are accounted for, and so is the negative ``lr_statistic`` that a finite top of the grid gives on Poisson data.
+
+    **dispersion_draws, dispersion_interval, dispersion_bias** (``interval=True``).  ``n_draws`` cohorts are drawn from the
+    negative-binomial fit at the estimate (``draw_nb_counts`` of the exposures fitted at ``dispersion``) and each is re-estimated on
+    the grid.  ``dispersion_interval`` holds the order statistics of those estimates at ``quantiles``, taken outward;
+    ``dispersion_bias = median(dispersion_draws) / dispersion``.  With many free exposures the maximum-likelihood ``alpha`` is
+    pushed upward (the exposures absorb part of the overdispersion; data drawn with ``alpha = 20``, N = 40, gave 17.8 at K = 3,
+    56 at (K, V) = (17, 33) and the top of the grid at K = 96): a bias well above 1 is that effect at your K, and the interval is
+    one of the biased estimator around the estimate, not a corrected one.
+
+    **Both statements are conditional on the grid.**  The estimate and every re-estimate are grid values; an estimate at the last
+    grid value (``at_upper_edge``) says "Poisson is adequate at this resolution", its draws mostly sit at the edge too, and the
+    interval then only says so.  The p-value is that of the statistic computed on this grid.
+
+    Draws are processed in chunks whose tiled problem list stays within ``chunk_bytes`` (default 256 MiB).  Anything out of range
+    is a ``ValueError`` before the device is touched."""
+    t_start = time.perf_counter()
+    X, S, _, seed, min_it, max_it, freq, tol, q, chunk = check_arguments(counts, signatures, 0, seed, quantiles, min_iterations, max_iterations,
+                                                                        conv_test_freq, tol, chunk_bytes)
+    check_integer_counts(X)
+    g = check_grid(grid)
+    B = check_n_draws(n_draws)
+    if not isinstance(interval, (bool, np.bool_)) or not isinstance(per_sample, (bool, np.bool_)):
+        raise ValueError("'interval' and 'per_sample' must be booleans.")
+    (N, V), A = X.shape, g.size
+    if A * N >= 2**31:
+        raise ValueError(f"{A} grid values x {N} samples: at most 2**31 - 1 problems.")
+    if interval and (X.sum(axis=1) > MAX_DRAW_MEAN).any():
+        raise ValueError("dispersion_test(interval=True) needs row totals of at most 2**24.")
+    it = (min_it, max_it, freq, tol)
+    kw = dict(min_iterations=min_it, max_iterations=max_it, conv_test_freq=freq, tol=tol, device=device)
+    est = estimate_dispersion(X, S, g, per_sample=per_sample, **kw)
+    # cohorts per chunk: the tiled [A N][V] lists of a chunk stay within chunk_bytes (at least one cohort)
+    per_chunk = int(max(1, min(B, (chunk if chunk > 0 else 256 << 20) // (8 * A * N * V), (2**31 - 1) // (A * N))))
+
+    def estimates(cohorts, poisson):
+        out_alpha, out_lr = [], []
+        for first in range(0, B, per_chunk):
+            part = cohorts[first:first + per_chunk]
+            profile, pois = _cohort_profiles(part, S, g, poisson, it, device)
+            for c in range(part.shape[0]):
+                a, _, lr = select_dispersion(g, profile[c], pois[c] if poisson else np.zeros(N), per_sample)
+                out_alpha.append(a), out_lr.append(lr)
+        return np.array(out_alpha), np.array(out_lr)
+
+    fit0 = refit_exposures(X, S, **kw)
+    _, null_lr = estimates(draw_model_counts(fit0.exposures, S, X.sum(axis=1), B, seed, device=device), True)
+    p_value = (1 + (null_lr >= est.lr_statistic).sum(axis=0)) / (B + 1)
+    res = DispersionTestResult(estimate=est, dispersion=est.dispersion, at_upper_edge=est.at_upper_edge, lr_statistic=est.lr_statistic,
+                               p_value=p_value if per_sample else float(p_value), null_lr=null_lr, quantiles=tuple(float(v) for v in q))
+    if interval:
+        best = np.searchsorted(g, np.broadcast_to(est.dispersion, (N,)))
+        H = est.exposures[best, np.arange(N)]  # every sample's exposures at the estimate
+        draws, _ = estimates(draw_nb_counts(H, S, est.dispersion, B, seed, device=device), False)
+        order = np.sort(draws, axis=0)
+        pos = np.asarray(q, dtype=np.float64) * (B - 1)
+        index = np.clip(np.where(np.asarray(q) <= 0.5, np.floor(pos), np.ceil(pos)).astype(np.int64), 0, B - 1)
+        res.dispersion_draws, res.dispersion_interval = draws, order[index]
+        res.dispersion_bias = np.median(draws, axis=0) / est.dispersion
+        if not per_sample:
+            res.dispersion_bias = float(res.dispersion_bias)
+    res.timings = {"total_s": time.perf_counter() - t_start, "cohorts_per_chunk": per_chunk}
+    return res
