@@ -20,7 +20,7 @@
 // trial count from the table's total; here the weights carry 40 bits each (a 32-bit table of 96 cells would leave a cell 25
 // bits) and the trial count comes from the sample.
 // The refits of the observed counts and of the draws are refit_kernel launches (salnmf_refit.h, built from its solve_* pieces); the
-// host driver uses the family's kit (salnmf_refit.hip): launch_tiles, Spans, chunk_rows, upload / download.
+// host driver is gof_run (salnmf_refit_drivers.h), which the negative-binomial test shares.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -68,7 +68,11 @@ struct RefitReduceArgs {
     int index[REFIT_MAX_QUANTILES];
 };
 
-#ifdef SALNMF_REFIT_KERNELS  // salnmf_refit.hip alone compiles the kernels (it includes salnmf_kernels.h first)
+// salnmf_refit.hip (the translation unit of refit_reduce_kernel): red.index as check_resamples left it (salnmf_host_kit.h), every
+// other member filled here -- the reduction of H [R][N][K] to the mean and the Q order statistics of every (sample, signature)
+void refit_launch_reduce(RefitReduceArgs& red, const double* H, double* quant, double* mean, int64_t N, int K, int R, int Q, hipStream_t stream);
+
+#ifdef SALNMF_REFIT_KERNELS  // the tile-solve pieces and refit_kernel, for the units that instantiate tile-solve kernels (salnmf_kernels.h first)
 
 // One problem's KL divergence from the lane's 24 entries (rows v = 16 vt + 4 r + q of column c16): forward mode 1's term
 // (salnmf_forward_kernel.h) per entry, the lane's entries in (vt, r) order, then the four q groups by rows_sum -- the same
@@ -254,6 +258,9 @@ __global__ void __launch_bounds__(BLOCK) refit_kernel(RefitArgs a) {
         }
     }
 }
+#endif  // SALNMF_REFIT_KERNELS
+
+#ifdef SALNMF_REFIT_REDUCE_KERNEL  // salnmf_refit.hip alone: an ordinary kernel, defined once in the library (refit_launch_reduce)
 
 // One workgroup per sample n: the mean over r of every signature's exposure (thread k, ascending r), then per signature
 // the R values sorted in LDS (bitonic, padded with +inf to a power of two) and the order statistics the host asked for.
@@ -286,6 +293,6 @@ __global__ void __launch_bounds__(REFIT_SORT_BLOCK) refit_reduce_kernel(RefitRed
         __syncthreads();
     }
 }
-#endif  // SALNMF_REFIT_KERNELS
+#endif  // SALNMF_REFIT_REDUCE_KERNEL
 
 }  // namespace salnmf

@@ -10,15 +10,16 @@
 // (salnmf_exposure_change; salnmf_change.h: change_kernel here, change_draw_kernel in salnmf_batch.hip); and of
 // the per-signature test of a changed share (salnmf_signature_change; salnmf_sigchange.h: sigchange_kernel here, sigchange_draw_kernel in
 // salnmf_batch.hip), DESIGN.md section 22.  The six tile-solve kernels share the solve_* pieces of salnmf_refit.h; the drivers below share one kit:
-// launch_tiles, fill_reduce, from salnmf_host_kit.h Spans, chunk_rows and upload / download, and for the pair calls pair_observed and
-// pair_draw_solve.
+// from salnmf_host_kit.h launch_tiles, the argument checks, Spans, chunk_rows and upload / download; from salnmf_refit_drivers.h
+// bootstrap_refit, gof_run and draw_run, which the negative-binomial entry points of salnmf_nb.hip call too; refit_launch_reduce
+// here, next to its kernel; and for the pair calls pair_observed and pair_draw_solve.
 #define SALNMF_TEMPLATES_ONLY 1
 #define SALNMF_REFIT_KERNELS 1
+#define SALNMF_REFIT_REDUCE_KERNEL 1
 #include "../../include/salnmf.h"
 #include "salnmf_kernels.h"
 #include "salnmf_device.h"
-#include "salnmf_host_kit.h"
-#include "salnmf_refit.h"
+#include "salnmf_refit_drivers.h"
 #include "salnmf_assign.h"
 #include "salnmf_gof.h"
 #include "salnmf_presence.h"
@@ -38,8 +39,8 @@ using namespace salnmf;
 
 namespace {
 
-// What both entry points check and prepare before any launch: the ranges, the signatures, the counts clipped to EPSILON
-// (and as integers for the resampler when R > 0), the quantiles' indices, the device and its CU count.
+// What the refit, the assignment, the goodness-of-fit test and the pair calls check and prepare before any launch: the checks of
+// salnmf_host_kit.h in their order, with the assignment's sets between the ranges and the signatures, then the device and its CU count.
 struct RefitInputs {
     std::vector<double> x;
     std::vector<uint32_t> icounts;
@@ -58,15 +59,7 @@ struct AssignSets {
 int refit_prepare(int device, const double* counts, int64_t N, int V, const double* signatures, int K, int R, int Q, const double* quantiles,
                   int min_iterations, int max_iterations, int conv_test_freq, double tol, bool resample_outputs, RefitInputs& in,
                   const AssignSets& sets = AssignSets{}) {
-    if (N < 1 || N > 0x7fffffff) return fail("n_samples must be in [1, 2^31), got %lld", (long long)N);
-    if (V < 1 || V > VMAX) return fail("n_features must be in [1, %d], got %d", VMAX, V);
-    if (K < 1 || K > REFIT_KMAX) return fail("n_signatures must be in [1, %d], got %d", REFIT_KMAX, K);
-    if (R < 0 || R > REFIT_SORT_MAX) return fail("n_resamples must be in [0, %d], got %d", REFIT_SORT_MAX, R);
-    if (min_iterations < 0 || max_iterations < min_iterations) return fail("need 0 <= min_iterations <= max_iterations, got %d and %d", min_iterations, max_iterations);
-    if (conv_test_freq < 1) return fail("conv_test_freq must be positive, got %d", conv_test_freq);
-    if (!(tol >= 0.0) || !std::isfinite(tol)) return fail("tol must be finite and not negative, got %g", tol);
-    if (Q < 0 || Q > REFIT_MAX_QUANTILES) return fail("n_quantiles must be in [0, %d], got %d", REFIT_MAX_QUANTILES, Q);
-    if (R > 0 && !resample_outputs) return fail("null output for the resamples");
+    CK(check_refit_ranges(N, V, K, R, min_iterations, max_iterations, conv_test_freq, tol, Q, resample_outputs));
     if (sets.readd != 0 && sets.readd != 1) return fail("readd must be 0 or 1, got %d", sets.readd);
     const int words = ((K + 15) / 16 + 1) / 2;  // assign_kernel<KT>: NW
     auto pack = [&](const uint8_t* set, std::vector<uint32_t>& out) {
@@ -92,61 +85,16 @@ int refit_prepare(int device, const double* counts, int64_t N, int V, const doub
                     return fail("sample %lld: required signature %d is not a candidate", (long long)(i / words), 32 * (int)(i % words) + __builtin_ctz(off));
                 }
     }
-    for (int k = 0; k < K; ++k) {
-        double sum = 0.0;
-        for (int v = 0; v < V; ++v) {
-            const double w = signatures[(size_t)k * V + v];
-            if (!std::isfinite(w) || w < 0.0) return fail("signature %d, feature %d: entries must be finite and not negative, got %g", k, v, w);
-            sum += w;
-        }
-        if (!(sum > 0.0) || !std::isfinite(sum)) return fail("signature %d needs a positive finite sum", k);
-    }
-    std::vector<double>& x = in.x;
-    x.resize((size_t)N * V);
-    for (size_t i = 0; i < x.size(); ++i) {
-        if (!std::isfinite(counts[i]) || counts[i] < 0.0)
-            return fail("counts must be finite and not negative: row %lld, column %d holds %g", (long long)(i / V), (int)(i % V), counts[i]);
-        x[i] = counts[i] < SALNMF_EPSILON ? SALNMF_EPSILON : counts[i];
-    }
-    if (R > 0) {
-        CK(refit_check_counts(counts, N, V, in.icounts));
-        for (int i = 0; i < Q; ++i) {
-            const double qv = quantiles[i];
-            if (!(qv >= 0.0 && qv <= 1.0)) return fail("quantile %d must be in [0, 1], got %g", i, qv);
-            // an order statistic, taken outward
-            const double pos = qv * (double)(R - 1);
-            in.red.index[i] = std::min(R - 1, std::max(0, (int)(qv <= 0.5 ? std::floor(pos) : std::ceil(pos))));
-        }
-    }
+    CK(check_signatures(signatures, K, V));
+    CK(clip_counts(counts, N, V, in.x));
+    if (R > 0) CK(check_resamples(counts, N, V, R, Q, quantiles, in.icounts, in.red.index));
     hipDeviceProp_t prop;
     CK(open_device(device, &prop));
     in.cus = prop.multiProcessorCount;
     return 0;
 }
 
-// ---- the host kit of the family: one tile launcher and one reduce fill here; the span timer, the chunk
-// rule and the copies in salnmf_host_kit.h.
-
-// What every tile-solve kernel's launch does: one workgroup per CU (the kernels' registers leave room for one wave per SIMD; waves
-// fetch tiles until the list is empty), the list's head reset, and the instantiation for (K + 15) / 16 signature tiles, which
-// `launch` gets as a std::integral_constant.
-template <typename Launch>
-int launch_tiles(const char* what, int64_t P, int K, unsigned* next_tile, int cus, hipStream_t stream, Launch&& launch) {
-    const int64_t ntiles = (P + 15) / 16;
-    const dim3 grid((unsigned)std::min<int64_t>((int64_t)cus, (ntiles + WAVES - 1) / WAVES));
-    HIPCK(hipMemsetAsync(next_tile, 0, sizeof(unsigned), stream));
-    switch ((K + 15) / 16) {
-        case 1: launch(std::integral_constant<int, 1>{}, grid); break;
-        case 2: launch(std::integral_constant<int, 2>{}, grid); break;
-        case 3: launch(std::integral_constant<int, 3>{}, grid); break;
-        case 4: launch(std::integral_constant<int, 4>{}, grid); break;
-        case 5: launch(std::integral_constant<int, 5>{}, grid); break;
-        case 6: launch(std::integral_constant<int, 6>{}, grid); break;
-        default: return fail("no %s kernel for %d signatures", what, K);
-    }
-    HIPCK(hipGetLastError());
-    return 0;
-}
+// ---- the launchers of the tile-solve kernels (salnmf_host_kit.h: launch_tiles)
 
 int launch_refit(const RefitArgs& a, int cus, hipStream_t stream) {
     return launch_tiles("refit", a.P, a.K, a.next_tile, cus, stream,
@@ -172,15 +120,15 @@ int launch_profile(const ProfileArgs& a, int cus, hipStream_t stream) {
                         [&](auto kt, dim3 grid) { hipLaunchKernelGGL(profile_kernel<decltype(kt)::value>, grid, dim3(BLOCK), 0, stream, a); });
 }
 
-// The resamples' reduction over H [R][N][K] (red.index is refit_prepare's)
-void fill_reduce(RefitReduceArgs& red, const double* H, double* quant, double* mean, int64_t N, int K, int R, int Q) {
+}  // namespace
+
+void salnmf::refit_launch_reduce(RefitReduceArgs& red, const double* H, double* quant, double* mean, int64_t N, int K, int R, int Q, hipStream_t stream) {
     red.H = H, red.quant = quant, red.mean = mean;
     red.N = N, red.K = K, red.R = R, red.Q = Q;
     red.R2 = 1;
     while (red.R2 < R) red.R2 <<= 1;
+    hipLaunchKernelGGL(refit_reduce_kernel, dim3((unsigned)N), dim3(REFIT_SORT_BLOCK), 0, stream, red);
 }
-
-}  // namespace
 
 extern "C" int salnmf_refit_exposures(int device, const double* counts, int64_t n_samples, int n_features, const double* signatures, int n_signatures,
                                       int n_resamples, uint64_t seed, int n_quantiles, const double* quantiles, int min_iterations, int max_iterations,
@@ -193,84 +141,15 @@ extern "C" int salnmf_refit_exposures(int device, const double* counts, int64_t 
     RefitInputs in;
     CK(refit_prepare(device, counts, N, V, signatures, K, R, Q, quantiles, min_iterations, max_iterations, conv_test_freq, tol,
                      exposures_mean && n_iterations_resampled && errors_resampled && (Q <= 0 || (quantiles && exposures_quantiles)), in));
-    const std::vector<double>& x = in.x;
-    const std::vector<uint32_t>& icounts = in.icounts;
-    RefitReduceArgs& red = in.red;
-    const int cus = in.cus;
-
-    // resamples per chunk: the [chunk][N][V] buffer stays within chunk_bytes (at least one resample)
-    const int chunk = R > 0 ? (int)chunk_rows(chunk_bytes, sizeof(double) * (size_t)N * V, R) : 0;
-
     // (host buffers of the asynchronous copies live until d's destructor has waited for the stream)
     DevBufs d;
     CK(d.own_stream());
-    const size_t NR = (size_t)N * (size_t)std::max(R, 1);
     double* dW = upload(d, signatures, (size_t)K * V);
-    double* dX = upload(d, x);
-    double* dH = d.get<double>((size_t)N * K);
-    double* derr = d.get<double>((size_t)N);
-    int* dnit = d.get<int>((size_t)N);
-    int* dconv = d.get<int>((size_t)N);
-    unsigned* dnext = d.get<unsigned>(1);
-    if (!dW || !dX || !dH || !derr || !dnit || !dconv || !dnext) return fail("hipMalloc failed (refit of %lld samples)", (long long)N);
-    uint32_t* dcounts = nullptr;
-    double *dXr = nullptr, *dHr = nullptr, *derr_r = nullptr, *dquant = nullptr, *dmean = nullptr;
-    int *dnit_r = nullptr, *dconv_r = nullptr;
-    if (R > 0) {
-        dcounts = upload(d, icounts);
-        dXr = d.get<double>((size_t)chunk * N * V);
-        dHr = d.get<double>(NR * K);
-        derr_r = d.get<double>(NR);
-        dnit_r = d.get<int>(NR);
-        dconv_r = d.get<int>(NR);
-        dquant = d.get<double>((size_t)std::max(Q, 1) * N * K);
-        dmean = d.get<double>((size_t)N * K);
-        if (!dcounts || !dXr || !dHr || !derr_r || !dnit_r || !dconv_r || !dquant || !dmean)
-            return fail("hipMalloc failed (%d resamples of %lld x %d, %d signatures)", R, (long long)N, V, K);
-    }
-
-    RefitArgs a{dX, dW, dH, derr, dnit, dconv, dnext, N, V, K, min_iterations, max_iterations, conv_test_freq, tol};
-    Spans sp;  // resample, refit, reduce
-    sp.start(d, timings != nullptr);
-    CK(sp.timed(1, [&] { return launch_refit(a, cus, d.stream); }));
-    int n_chunks = 0;
-    for (int first = 0; first < R; first += chunk, ++n_chunks) {
-        const int count = std::min(chunk, R - first);
-        CK(sp.timed(0, [&]() -> int {
-            refit_launch_resample(dcounts, dXr, N, V, seed, first, count, d.stream);
-            HIPCK(hipGetLastError());
-            return 0;
-        }));
-        RefitArgs c = a;
-        c.X = dXr;
-        c.P = (int64_t)count * N;
-        c.H = dHr + (size_t)first * N * K;
-        c.err = derr_r + (size_t)first * N;
-        c.nit = dnit_r + (size_t)first * N;
-        c.conv = dconv_r + (size_t)first * N;
-        CK(sp.timed(1, [&] { return launch_refit(c, cus, d.stream); }));
-    }
-    if (R > 0) {
-        fill_reduce(red, dHr, dquant, dmean, N, K, R, Q);
-        CK(sp.timed(2, [&]() -> int {
-            hipLaunchKernelGGL(refit_reduce_kernel, dim3((unsigned)N), dim3(REFIT_SORT_BLOCK), 0, d.stream, red);
-            HIPCK(hipGetLastError());
-            return 0;
-        }));
-        if (Q > 0) CK(download(d, exposures_quantiles, dquant, (size_t)Q * N * K));
-        CK(download(d, exposures_mean, dmean, (size_t)N * K));
-        CK(download(d, n_iterations_resampled, dnit_r, NR));
-        CK(download(d, errors_resampled, derr_r, NR));
-        if (exposures_resampled) CK(download(d, exposures_resampled, dHr, NR * K));
-    }
-    CK(download(d, exposures, dH, (size_t)N * K));
-    CK(download(d, errors, derr, (size_t)N));
-    CK(download(d, n_iterations, dnit, (size_t)N));
-    CK(download(d, converged, dconv, (size_t)N));
-    HIPCK(hipStreamSynchronize(d.stream));
-    CK(sp.totals(3, timings));
-    if (timings) timings[3] = (double)n_chunks;
-    return 0;
+    double* dX = upload(d, in.x);
+    const RefitArgs a{dX, dW, nullptr, nullptr, nullptr, nullptr, nullptr, N, V, K, min_iterations, max_iterations, conv_test_freq, tol};
+    const BootstrapRun io{R, Q, bootstrap_chunk(chunk_bytes, N, V, R), seed, in.icounts, in.red, in.cus, exposures, errors, n_iterations, converged,
+                          exposures_quantiles, exposures_mean, n_iterations_resampled, errors_resampled, exposures_resampled, timings};
+    return bootstrap_refit(d, "refit", dW && dX, a, io, launch_refit);
 }
 
 extern "C" int salnmf_assign_signatures(int device, const double* counts, int64_t n_samples, int n_features, const double* signatures, int n_signatures,
@@ -309,7 +188,7 @@ extern "C" int salnmf_assign_signatures_ex(int device, const double* counts, int
     CK(refit_prepare(device, counts, N, V, signatures, K, R, Q, quantiles, min_iterations, max_iterations, conv_test_freq, tol,
                      selection_frequency && exposures_mean && (Q <= 0 || (quantiles && exposures_quantiles)), in, AssignSets{candidates, required, readd}));
     const int cus = in.cus;
-    const int chunk = R > 0 ? (int)chunk_rows(chunk_bytes, sizeof(double) * (size_t)N * V, R) : 0;
+    const int chunk = bootstrap_chunk(chunk_bytes, N, V, R);
 
     DevBufs d;
     CK(d.own_stream());
@@ -384,11 +263,9 @@ extern "C" int salnmf_assign_signatures_ex(int device, const double* counts, int
         CK(sp.timed(1, [&] { return launch_assign(c, cus, d.stream); }));
     }
     if (R > 0) {
-        RefitReduceArgs& red = in.red;
-        fill_reduce(red, dHr, dquant, dmean, N, K, R, Q);
         const AssignSelectArgs sel{dHr, dfreq, (int64_t)NK, R};
         CK(sp.timed(2, [&]() -> int {
-            hipLaunchKernelGGL(refit_reduce_kernel, dim3((unsigned)N), dim3(REFIT_SORT_BLOCK), 0, d.stream, red);
+            refit_launch_reduce(in.red, dHr, dquant, dmean, N, K, R, Q, d.stream);
             HIPCK(hipGetLastError());
             hipLaunchKernelGGL(assign_selection_kernel, dim3((unsigned)((NK + 255) / 256)), dim3(256), 0, d.stream, sel);
             HIPCK(hipGetLastError());
@@ -423,26 +300,12 @@ extern "C" int salnmf_assign_signatures_ex(int device, const double* counts, int
 
 // ---- goodness of fit by parametric bootstrap (salnmf_gof.h)
 
-static int gof_check_draws(int n_draws) {
-    if (n_draws < 1 || n_draws > GOF_MAX_DRAWS) return fail("n_draws must be in [1, %d], got %d", GOF_MAX_DRAWS, n_draws);
-    return 0;
-}
-
 extern "C" int salnmf_draw_model_counts(int device, const double* exposures, int64_t n_samples, int n_signatures, const double* signatures,
                                         int n_features, const double* totals, int n_draws, uint64_t seed, double* out) {
     const int64_t N = n_samples;
     const int V = n_features, K = n_signatures, B = n_draws;
     if (!exposures || !signatures || !totals || !out) return fail("null argument");
-    if (N < 1 || N > 0x7fffffff) return fail("n_samples must be in [1, 2^31), got %lld", (long long)N);
-    if (V < 1 || V > GOF_VMAX) return fail("n_features must be in [1, %d], got %d", GOF_VMAX, V);
-    if (K < 1 || K > GOF_KMAX) return fail("n_signatures must be in [1, %d], got %d", GOF_KMAX, K);
-    CK(gof_check_draws(B));
-    for (size_t i = 0; i < (size_t)N * K; ++i)
-        if (!std::isfinite(exposures[i]) || exposures[i] < 0.0)
-            return fail("exposures must be finite and not negative: row %lld, signature %d holds %g", (long long)(i / K), (int)(i % K), exposures[i]);
-    for (size_t i = 0; i < (size_t)K * V; ++i)
-        if (!std::isfinite(signatures[i]) || signatures[i] < 0.0)
-            return fail("signature %d, feature %d: entries must be finite and not negative, got %g", (int)(i / V), (int)(i % V), signatures[i]);
+    CK(check_model_draw(exposures, N, K, signatures, V, B));
     std::vector<uint32_t> trials((size_t)N);
     for (int64_t n = 0; n < N; ++n) {
         const double t = totals[n];
@@ -452,21 +315,14 @@ extern "C" int salnmf_draw_model_counts(int device, const double* exposures, int
     }
     hipDeviceProp_t prop;
     CK(open_device(device, &prop));
-    const size_t NV = (size_t)N * V;
-    const int chunk = (int)chunk_rows(0, sizeof(double) * NV, B);
     DevBufs d;
     CK(d.own_stream());
     double* dH = upload(d, exposures, (size_t)N * K);
     double* dW = upload(d, signatures, (size_t)K * V);
     uint32_t* dT = upload(d, trials);
-    double* dout = d.get<double>((size_t)chunk * NV);
-    if (!dH || !dW || !dT || !dout) return fail("hipMalloc failed (%d draws of %lld x %d)", chunk, (long long)N, V);
-    for (int first = 0; first < B; first += chunk) {
-        const int count = std::min(chunk, B - first);
+    CK(draw_run(d, dH && dW && dT, N, V, B, out, [&](double* dout, int first, int count) {
         gof_launch_model_draw(dH, dW, dT, nullptr, dout, N, V, K, seed, 0.0, first, count, d.stream);
-        HIPCK(hipGetLastError());
-        CK(download(d, out + (size_t)first * NV, dout, (size_t)count * NV));
-    }
+    }));
     HIPCK(hipStreamSynchronize(d.stream));
     return 0;
 }
@@ -479,79 +335,24 @@ extern "C" int salnmf_goodness_of_fit(int device, const double* counts, int64_t 
     const int V = n_features, K = n_signatures, B = n_draws;
     if (!counts || !signatures || !exposures || !errors || !n_iterations || !converged || !n_exceed || !null_mean || !null_errors || !null_n_iterations)
         return fail("null argument");
-    CK(gof_check_draws(B));
+    CK(check_n_draws(B));
     RefitInputs in;
     CK(refit_prepare(device, counts, N, V, signatures, K, 0, 0, nullptr, min_iterations, max_iterations, conv_test_freq, tol, true, in));
     CK(refit_check_counts(counts, N, V, in.icounts));  // integer counts, row totals below 2^32 (the values themselves are not used)
-    const int cus = in.cus;
-    const size_t NV = (size_t)N * V, NK = (size_t)N * K, NB = (size_t)N * B;
-
-    // draws per chunk: the [chunk][N][V] buffer stays within chunk_bytes (at least one draw)
-    const int chunk = (int)chunk_rows(chunk_bytes, sizeof(double) * NV, B);
 
     DevBufs d;
     CK(d.own_stream());
     double* dW = upload(d, signatures, (size_t)K * V);
     double* dX = upload(d, in.x);
-    double* dH = d.get<double>(NK);
-    double* derr = d.get<double>((size_t)N);
-    int* dnit = d.get<int>((size_t)N);
-    int* dconv = d.get<int>((size_t)N);
-    unsigned* dnext = d.get<unsigned>(1);
-    double* dXb = d.get<double>((size_t)chunk * NV);
-    double* dHb = d.get<double>((size_t)chunk * NK);
-    double* derr_b = d.get<double>(NB);
-    int* dnit_b = d.get<int>(NB);
-    int* dconv_b = d.get<int>((size_t)chunk * N);
-    int* dexceed = d.get<int>((size_t)N);
-    double* dmean = d.get<double>((size_t)N);
-    if (!dW || !dX || !dH || !derr || !dnit || !dconv || !dnext || !dXb || !dHb || !derr_b || !dnit_b || !dconv_b || !dexceed || !dmean)
-        return fail("hipMalloc failed (%d draws of %lld x %d, %d signatures)", B, (long long)N, V, K);
-
-    Spans sp;  // draw, refit, reduce
-    sp.start(d, timings != nullptr);
-    const RefitArgs a{dX, dW, dH, derr, dnit, dconv, dnext, N, V, K, min_iterations, max_iterations, conv_test_freq, tol};
-    CK(sp.timed(1, [&] { return launch_refit(a, cus, d.stream); }));
-    int n_chunks = 0;
-    for (int first = 0; first < B; first += chunk, ++n_chunks) {
-        const int count = std::min(chunk, B - first);
-        // from the device-resident exposures of the observed refit; a row's trial count is read off the clipped counts
-        CK(sp.timed(0, [&]() -> int {
+    const RefitArgs a{dX, dW, nullptr, nullptr, nullptr, nullptr, nullptr, N, V, K, min_iterations, max_iterations, conv_test_freq, tol};
+    const GofRun io{B, (int)chunk_rows(chunk_bytes, sizeof(double) * (size_t)N * V, B), in.cus, exposures, errors, n_iterations, converged, n_exceed,
+                    null_mean, null_errors, null_n_iterations, draws, timings};
+    return gof_run(
+        d, dW && dX, a, io, launch_refit,
+        [&](const double* dH, double* dXb, int first, int count) {  // a row's trial count is read off the clipped counts
             gof_launch_model_draw(dH, dW, nullptr, dX, dXb, N, V, K, seed, SALNMF_EPSILON, first, count, d.stream);
-            HIPCK(hipGetLastError());
-            return 0;
-        }));
-        if (draws) CK(download(d, draws + (size_t)first * NV, dXb, (size_t)count * NV));
-        RefitArgs c = a;
-        c.X = dXb;
-        c.P = (int64_t)count * N;
-        c.H = dHb;
-        c.err = derr_b + (size_t)first * N;
-        c.nit = dnit_b + (size_t)first * N;
-        c.conv = dconv_b;
-        CK(sp.timed(1, [&] { return launch_refit(c, cus, d.stream); }));
-    }
-    const GofReduceArgs red{derr, derr_b, dexceed, dmean, N, B};
-    CK(sp.timed(2, [&]() -> int {
-        gof_launch_reduce(red, d.stream);
-        HIPCK(hipGetLastError());
-        return 0;
-    }));
-    CK(download(d, exposures, dH, NK));
-    CK(download(d, errors, derr, (size_t)N));
-    CK(download(d, n_iterations, dnit, (size_t)N));
-    CK(download(d, converged, dconv, (size_t)N));
-    CK(download(d, n_exceed, dexceed, (size_t)N));
-    CK(download(d, null_mean, dmean, (size_t)N));
-    CK(download(d, null_errors, derr_b, NB));
-    CK(download(d, null_n_iterations, dnit_b, NB));
-    HIPCK(hipStreamSynchronize(d.stream));
-    if (draws)  // plain counts: the clipped zeros restored to 0
-        for (size_t i = 0; i < (size_t)B * NV; ++i)
-            if (draws[i] < 1.0) draws[i] = 0.0;
-    CK(sp.totals(3, timings));
-    if (timings) timings[3] = (double)n_chunks;
-    return 0;
+        },
+        [] { return 0; });  // (no download of its own)
 }
 
 // ---- the pair run: what the presence test (salnmf_presence.h), its power analysis (salnmf_power.h, section
@@ -755,7 +556,7 @@ int presence_enqueue(const PairIO& io, int64_t other_rows, PairRun& r) {
     if (!io.counts || !io.signatures || !io.test || !io.tested || !io.statistic || !io.n_exceed || !io.null_mean || !io.exposures || !io.errors ||
         !io.null_exposures || !io.null_errors || !io.n_iterations || !io.converged || !io.null_statistics || !io.null_n_iterations)
         return fail("null argument");
-    CK(gof_check_draws(B));
+    CK(check_n_draws(B));
     CK(pair_observed(io, true, 1, r));
     const size_t NS = (size_t)N * S, NP = r.NP;
     const double nan = std::nan("");
@@ -875,7 +676,7 @@ extern "C" int salnmf_signature_power(int device, const double* counts, int64_t 
                                       int* alt_n_iterations, int* alt_n_exceed, int* n_detected, double* alt_mean, double* alt_draws, double* timings) {
     const int L = n_shares, A = n_alt_draws, B = n_draws;
     if (!shares || !planted_exposures || !alt_statistics || !alt_n_iterations || !alt_n_exceed || !n_detected || !alt_mean) return fail("null argument");
-    CK(gof_check_draws(B));
+    CK(check_n_draws(B));
     if (L < 1 || L > POWER_MAX_SHARES) return fail("n_shares must be in [1, %d], got %d", POWER_MAX_SHARES, L);
     for (int l = 0; l < L; ++l) {
         if (!std::isfinite(shares[l]) || shares[l] < 0.0 || shares[l] >= 1.0) return fail("share %d must be finite and in [0, 1), got %g", l, shares[l]);
@@ -1143,7 +944,7 @@ extern "C" int salnmf_exposure_change(int device, const double* counts_a, int64_
     if (n_samples_b != N || n_features_b != V)
         return fail("row n of counts_a and row n of counts_b form pair n: the shapes must agree, got %lld x %d and %lld x %d", (long long)N, V,
                     (long long)n_samples_b, n_features_b);
-    CK(gof_check_draws(B));
+    CK(check_n_draws(B));
     if (conv_test_freq >= 1 && max_iterations >= 0 && max_iterations % conv_test_freq != 0)
         return fail("max_iterations must be a multiple of conv_test_freq, got %d and %d", max_iterations, conv_test_freq);
     // the host ends of the asynchronous copies live until d's destructor has waited for the stream: d is declared after them
@@ -1318,7 +1119,7 @@ extern "C" int salnmf_signature_change(int device, const double* counts_a, int64
     if (n_samples_b != N || n_features_b != V)
         return fail("row n of counts_a and row n of counts_b form pair n: the shapes must agree, got %lld x %d and %lld x %d", (long long)N, V,
                     (long long)n_samples_b, n_features_b);
-    CK(gof_check_draws(B));
+    CK(check_n_draws(B));
     if (conv_test_freq >= 1 && max_iterations >= 0 && max_iterations % conv_test_freq != 0)
         return fail("max_iterations must be a multiple of conv_test_freq, got %d and %d", max_iterations, conv_test_freq);
     // the host ends of the asynchronous copies live until d's destructor has waited for the stream: d is declared after them

@@ -58,30 +58,68 @@ def check_integer_counts(X) -> np.ndarray:
     return X
 
 
-def draw_model_counts(exposures, signatures, totals, n_draws: int, seed: int = 0, device: int = 0) -> np.ndarray:
-    """``n_draws`` count matrices drawn from the model ``exposures (N, K) @ signatures (K, V)``: ``(n_draws, N, V)`` float64 of
-    integer values, row n of every draw a multinomial draw of ``totals[n]`` trials from the spectrum of row n (the contract:
-    ``include/salnmf.h``).  The signature rows are divided by their sums; the exposures are finite and non-negative, the totals
-    integers in [0, 2**32).  The same bits on every run, and draw b does not depend on ``n_draws``."""
+def check_model(exposures, signatures):
+    """``(H (N, K), S (K, V))`` of a fitted model, or ``ValueError``: the signature rows divided by their sums, the exposures
+    finite and non-negative with one column per signature and at least one row."""
     S = normalize_signatures(signatures)
-    K, V = S.shape
+    K = S.shape[0]
     H = np.ascontiguousarray(exposures, dtype=np.float64)
     if H.ndim != 2 or H.shape[0] < 1 or H.shape[1] != K:
         raise ValueError(f"'exposures' must be a matrix (samples x {K} signatures) with at least one row.")
     if not np.isfinite(H).all() or (H < 0).any():
         raise ValueError("Exposures must be finite and non-negative.")
+    return H, S
+
+
+def draw_model_counts(exposures, signatures, totals, n_draws: int, seed: int = 0, device: int = 0) -> np.ndarray:
+    """``n_draws`` count matrices drawn from the model ``exposures (N, K) @ signatures (K, V)``: ``(n_draws, N, V)`` float64 of
+    integer values, row n of every draw a multinomial draw of ``totals[n]`` trials from the spectrum of row n (the contract:
+    ``include/salnmf.h``).  The signature rows are divided by their sums; the exposures are finite and non-negative, the totals
+    integers in [0, 2**32).  The same bits on every run, and draw b does not depend on ``n_draws``."""
+    H, S = check_model(exposures, signatures)
+    (N, K), V = H.shape, S.shape[1]
     T = np.ascontiguousarray(totals, dtype=np.float64)
     if T.shape != (H.shape[0],):
         raise ValueError("'totals' must hold one trial count per row of the exposures.")
     if not np.isfinite(T).all() or (T < 0).any() or (T != np.floor(T)).any() or (T >= 2.0**32).any():
         raise ValueError("Totals must be non-negative integers below 2**32.")
     B, seed = check_n_draws(n_draws), check_seed(seed)
-    N = H.shape[0]
     lib = _lib.load_with_device()
     out = np.empty((B, N, V), dtype=np.float64)
     p = _lib.pointer
     _lib.check(lib.salnmf_draw_model_counts(int(device), p(H), N, K, p(S), V, p(T), B, seed, p(out)))
     return out
+
+
+def call_gof(symbol, model_args, X, S, B, seed, min_it, max_it, freq, tol, chunk, keep_draws, device, t_start, count_failed=False):
+    """One ``salnmf_*goodness_of_fit`` call on checked arguments: the outputs' allocation, the call of ``symbol`` with
+    ``model_args`` (the model's own arrays) after K and, with ``count_failed``, a trailing output for the rows no draw could
+    be made for.  Returns ``(the fields of a GofResult, that count)``."""
+    (N, V), K = X.shape, S.shape[0]
+    lib = _lib.load_with_device()
+
+    H = np.empty((N, K), dtype=np.float64)
+    err = np.empty(N, dtype=np.float64)
+    nit = np.empty(N, dtype=np.int32)
+    conv = np.empty(N, dtype=np.int32)
+    exceed = np.empty(N, dtype=np.int32)
+    mean = np.empty(N, dtype=np.float64)
+    err_b = np.empty((B, N), dtype=np.float64)
+    nit_b = np.empty((B, N), dtype=np.int32)
+    drawn = np.empty((B, N, V), dtype=np.float64) if keep_draws else None
+    failed = np.zeros(1, dtype=np.int32)
+    ms = (c_double * 4)()
+    p = _lib.pointer
+    _lib.check(getattr(lib, symbol)(
+        int(device), p(X), N, V, p(S), K, *(p(m) for m in model_args), B, seed, min_it, max_it, freq, tol, chunk,
+        p(H), p(err), p(nit), p(conv), p(exceed), p(mean), p(err_b), p(nit_b), p(drawn), ctypes.cast(ms, _lib._D), *([p(failed)] if count_failed else []),
+    ))
+    timings = {"draw_s": ms[0] / 1e3, "refit_s": ms[1] / 1e3, "reduce_s": ms[2] / 1e3, "refit_kernel_ms": ms[1], "n_chunks": int(ms[3]),
+               "total_s": time.perf_counter() - t_start}
+    fields = dict(exposures=H, reconstruction_errors=err, n_iterations=nit, converged=conv.astype(bool), n_exceed=exceed,
+                  p_value=(1 + exceed.astype(np.int64)) / (B + 1), null_mean=mean, null_errors=err_b, null_n_iterations=nit_b, draws=drawn,
+                  timings=timings)
+    return fields, int(failed[0])
 
 
 def goodness_of_fit(counts, signatures, n_draws: int = 200, seed: int = 0, min_iterations: int = 500, max_iterations: int = 10000,
@@ -102,26 +140,5 @@ def goodness_of_fit(counts, signatures, n_draws: int = 200, seed: int = 0, min_i
                                                                         conv_test_freq, tol, chunk_bytes)
     check_integer_counts(X)
     B = check_n_draws(n_draws)
-    (N, V), K = X.shape, S.shape[0]
-    lib = _lib.load_with_device()
-
-    H = np.empty((N, K), dtype=np.float64)
-    err = np.empty(N, dtype=np.float64)
-    nit = np.empty(N, dtype=np.int32)
-    conv = np.empty(N, dtype=np.int32)
-    exceed = np.empty(N, dtype=np.int32)
-    mean = np.empty(N, dtype=np.float64)
-    err_b = np.empty((B, N), dtype=np.float64)
-    nit_b = np.empty((B, N), dtype=np.int32)
-    drawn = np.empty((B, N, V), dtype=np.float64) if keep_draws else None
-    ms = (c_double * 4)()
-    p = _lib.pointer
-    _lib.check(lib.salnmf_goodness_of_fit(
-        int(device), p(X), N, V, p(S), K, B, seed, min_it, max_it, freq, tol, chunk,
-        p(H), p(err), p(nit), p(conv), p(exceed), p(mean), p(err_b), p(nit_b), p(drawn), ctypes.cast(ms, _lib._D),
-    ))
-    timings = {"draw_s": ms[0] / 1e3, "refit_s": ms[1] / 1e3, "reduce_s": ms[2] / 1e3, "refit_kernel_ms": ms[1], "n_chunks": int(ms[3]),
-               "total_s": time.perf_counter() - t_start}
-    return GofResult(exposures=H, reconstruction_errors=err, n_iterations=nit, converged=conv.astype(bool), n_exceed=exceed,
-                     p_value=(1 + exceed.astype(np.int64)) / (B + 1), null_mean=mean, null_errors=err_b, null_n_iterations=nit_b, draws=drawn,
-                     timings=timings)
+    fields, _ = call_gof("salnmf_goodness_of_fit", (), X, S, B, seed, min_it, max_it, freq, tol, chunk, keep_draws, device, t_start)
+    return GofResult(**fields)

@@ -15,16 +15,14 @@ dispersion estimate: a p-value for ``lr_statistic`` and an interval for the esti
 
 from __future__ import annotations
 
-import ctypes
 import time
-from ctypes import c_double
 from dataclasses import dataclass, field
 
 import numpy as np
 
 from . import _lib
-from .gof import check_integer_counts, check_n_draws, draw_model_counts
-from .refit import RefitResult, check_arguments, normalize_signatures, refit_exposures
+from .gof import GofResult, call_gof, check_integer_counts, check_model, check_n_draws, draw_model_counts
+from .refit import RefitResult, call_refit, check_arguments, quantile_indices, refit_exposures
 from .resample import check_seed
 
 EPSILON = float(np.finfo(np.float32).eps)
@@ -107,28 +105,6 @@ def poisson_constant(counts) -> np.ndarray:
     return (x * np.log(x) - x - gammaln(x + 1.0)).sum(axis=1)
 
 
-def _call(X, S, alpha, R, seed, q, min_it, max_it, freq, tol, chunk, keep_resamples, device):
-    (N, V), K = X.shape, S.shape[0]
-    lib = _lib.load_with_device()
-    Q = int(q.size)
-    H = np.empty((N, K), dtype=np.float64)
-    err = np.empty(N, dtype=np.float64)
-    nit = np.empty(N, dtype=np.int32)
-    conv = np.empty(N, dtype=np.int32)
-    Hq = np.empty((Q, N, K), dtype=np.float64) if R else None
-    Hm = np.empty((N, K), dtype=np.float64) if R else None
-    nit_r = np.empty((R, N), dtype=np.int32) if R else None
-    err_r = np.empty((R, N), dtype=np.float64) if R else None
-    Hr = np.empty((R, N, K), dtype=np.float64) if R and keep_resamples else None
-    ms = (c_double * 4)()
-    p = _lib.pointer
-    _lib.check(lib.salnmf_nb_refit_exposures(
-        int(device), p(X), N, V, p(S), K, p(alpha), R, seed, Q if R else 0, p(q), min_it, max_it, freq, tol, chunk,
-        p(H), p(err), p(nit), p(conv), p(Hq), p(Hm), p(nit_r), p(err_r), p(Hr), ctypes.cast(ms, _lib._D),
-    ))
-    return H, err, nit, conv, Hq, Hm, nit_r, err_r, Hr, ms
-
-
 def nb_refit_exposures(counts, signatures, dispersion, n_resamples: int = 0, resample_seed: int = 0, quantiles=(0.025, 0.5, 0.975),
                        min_iterations: int = 500, max_iterations: int = 10000, conv_test_freq: int = 10, tol: float = 1e-7,
                        keep_resamples: bool = False, device: int = 0, chunk_bytes: int | None = None) -> NBRefitResult:
@@ -146,12 +122,8 @@ def nb_refit_exposures(counts, signatures, dispersion, n_resamples: int = 0, res
     X, S, R, seed, min_it, max_it, freq, tol, q, chunk = check_arguments(counts, signatures, n_resamples, resample_seed, quantiles, min_iterations,
                                                                          max_iterations, conv_test_freq, tol, chunk_bytes)
     alpha = check_dispersion(dispersion, X.shape[0])
-    H, err, nit, conv, Hq, Hm, nit_r, err_r, Hr, ms = _call(X, S, alpha, R, seed, q, min_it, max_it, freq, tol, chunk, keep_resamples, device)
-    timings = {"resample_s": ms[0] / 1e3, "refit_s": ms[1] / 1e3, "reduce_s": ms[2] / 1e3, "refit_kernel_ms": ms[1],
-               "n_chunks": int(ms[3]), "total_s": time.perf_counter() - t_start}
-    return NBRefitResult(exposures=H, reconstruction_errors=err, n_iterations=nit, converged=conv.astype(bool), exposures_quantiles=Hq,
-                         exposures_mean=Hm, n_iterations_resampled=nit_r, reconstruction_errors_resampled=err_r, exposures_resampled=Hr,
-                         quantiles=tuple(float(v) for v in q), timings=timings, dispersion=alpha, log_likelihood=-err + nb_constant(X, alpha))
+    fit = call_refit("salnmf_nb_refit_exposures", (alpha,), X, S, R, seed, q, min_it, max_it, freq, tol, chunk, keep_resamples, device, t_start)
+    return NBRefitResult(**fit, dispersion=alpha, log_likelihood=-fit["reconstruction_errors"] + nb_constant(X, alpha))
 
 
 def select_dispersion(grid, profile, poisson_log_likelihood, per_sample: bool = False):
@@ -202,33 +174,28 @@ def estimate_dispersion(counts, signatures, grid=np.geomspace(1, 1e4, 17), per_s
     if A * N >= 2**31:
         raise ValueError(f"{A} grid values x {N} samples: at most 2**31 - 1 problems.")
     # problem (a, n) is row a N + n of the list: sample n at grid[a]
-    H, err, nit, conv, *_, ms = _call(np.ascontiguousarray(np.tile(X, (A, 1))), S, np.repeat(g, N), 0, 0, q, min_it, max_it, freq, tol, chunk, False, device)
-    divergence = err.reshape(A, N)
+    fit = call_refit("salnmf_nb_refit_exposures", (np.repeat(g, N),), np.ascontiguousarray(np.tile(X, (A, 1))), S, 0, 0, q, min_it, max_it, freq, tol,
+                     chunk, False, device)
+    H, nit, conv, ms = fit["exposures"], fit["n_iterations"], fit["converged"], fit["timings"]["refit_kernel_ms"]
+    divergence = fit["reconstruction_errors"].reshape(A, N)
     profile = np.stack([-divergence[a] + nb_constant(X, np.full(N, g[a])) for a in range(A)])
     poisson = refit_exposures(X, S, min_iterations=min_it, max_iterations=max_it, conv_test_freq=freq, tol=tol, device=device)
     poisson_ll = -poisson.reconstruction_errors + poisson_constant(X)
     dispersion, edge, lr = select_dispersion(g, profile, poisson_ll, per_sample)
-    timings = {"refit_s": ms[1] / 1e3, "refit_kernel_ms": ms[1], "poisson_refit_s": poisson.timings["refit_s"], "total_s": time.perf_counter() - t_start}
+    timings = {"refit_s": ms / 1e3, "refit_kernel_ms": ms, "poisson_refit_s": poisson.timings["refit_s"], "total_s": time.perf_counter() - t_start}
     return DispersionResult(grid=g, profile=profile, dispersion=dispersion, at_upper_edge=edge, poisson_log_likelihood=poisson_ll, lr_statistic=lr,
-                            exposures=H.reshape(A, N, K), divergence=divergence, n_iterations=nit.reshape(A, N), converged=conv.reshape(A, N).astype(bool),
+                            exposures=H.reshape(A, N, K), divergence=divergence, n_iterations=nit.reshape(A, N), converged=conv.reshape(A, N),
                             timings=timings)
 
 
 @dataclass
-class NBGofResult:
-    exposures: np.ndarray  # (N, K): the observed negative-binomial refit, as nb_refit_exposures returns it
-    reconstruction_errors: np.ndarray  # (N,): its negative-binomial divergences
-    n_iterations: np.ndarray  # (N,) int32
-    converged: np.ndarray  # (N,) bool
-    dispersion: np.ndarray  # (N,)
-    log_likelihood: np.ndarray  # (N,): -divergence + nb_constant(counts, dispersion)
-    n_exceed: np.ndarray  # (N,) int32: draws b with null_errors[b, n] >= reconstruction_errors[n]
-    p_value: np.ndarray  # (N,): (1 + n_exceed) / (B + 1)
-    null_mean: np.ndarray  # (N,): the sum of null_errors[:, n] in ascending b, divided by B
-    null_errors: np.ndarray  # (B, N)
-    null_n_iterations: np.ndarray  # (B, N) int32
-    draws: np.ndarray | None = None  # (B, N, V) with keep_draws
-    timings: dict = field(default_factory=dict)
+class NBGofResult(GofResult):
+    """:class:`GofResult <salamander_amd.gof.GofResult>` of the negative-binomial model: ``exposures`` as ``nb_refit_exposures``
+    returns them, ``reconstruction_errors`` and ``null_errors`` the negative-binomial divergences, plus the dispersions used and
+    the samples' log-likelihoods."""
+
+    dispersion: np.ndarray | None = None  # (N,)
+    log_likelihood: np.ndarray | None = None  # (N,): -divergence + nb_constant(counts, dispersion)
 
 
 @dataclass
@@ -258,14 +225,8 @@ def draw_nb_counts(exposures, signatures, dispersion, n_draws: int, seed: int = 
     vary, unlike ``draw_model_counts`` -- because the negative-binomial refit leaves the scale free.  The signature rows are
     divided by their sums; the exposures are finite and non-negative with row sums of at most 2**24; ``dispersion`` is a scalar
     or one value per row, in (0, 1e6].  The same bits on every run, and draw b does not depend on ``n_draws``."""
-    S = normalize_signatures(signatures)
-    K, V = S.shape
-    H = np.ascontiguousarray(exposures, dtype=np.float64)
-    if H.ndim != 2 or H.shape[0] < 1 or H.shape[1] != K:
-        raise ValueError(f"'exposures' must be a matrix (samples x {K} signatures) with at least one row.")
-    if not np.isfinite(H).all() or (H < 0).any():
-        raise ValueError("Exposures must be finite and non-negative.")
-    N = H.shape[0]
+    H, S = check_model(exposures, signatures)
+    (N, K), V = H.shape, S.shape[1]
     alpha = check_dispersion(dispersion, N)
     rows = np.flatnonzero(~((H @ S).sum(axis=1) <= MAX_DRAW_MEAN))
     if rows.size:
@@ -303,31 +264,10 @@ def nb_goodness_of_fit(counts, signatures, dispersion, n_draws: int = 200, seed:
         raise ValueError(f"nb_goodness_of_fit needs row totals of at most 2**24: row {int(rows[0])} sums to {X[int(rows[0])].sum():.0f}.")
     alpha = check_dispersion(dispersion, X.shape[0])
     B = check_n_draws(n_draws)
-    (N, V), K = X.shape, S.shape[0]
-    lib = _lib.load_with_device()
-
-    H = np.empty((N, K), dtype=np.float64)
-    err = np.empty(N, dtype=np.float64)
-    nit = np.empty(N, dtype=np.int32)
-    conv = np.empty(N, dtype=np.int32)
-    exceed = np.empty(N, dtype=np.int32)
-    mean = np.empty(N, dtype=np.float64)
-    err_b = np.empty((B, N), dtype=np.float64)
-    nit_b = np.empty((B, N), dtype=np.int32)
-    drawn = np.empty((B, N, V), dtype=np.float64) if keep_draws else None
-    failed = np.zeros(1, dtype=np.int32)
-    ms = (c_double * 4)()
-    p = _lib.pointer
-    _lib.check(lib.salnmf_nb_goodness_of_fit(
-        int(device), p(X), N, V, p(S), K, p(alpha), B, seed, min_it, max_it, freq, tol, chunk,
-        p(H), p(err), p(nit), p(conv), p(exceed), p(mean), p(err_b), p(nit_b), p(drawn), ctypes.cast(ms, _lib._D), p(failed),
-    ))
-    _failed_rows(int(failed[0]), "nb_goodness_of_fit")
-    timings = {"draw_s": ms[0] / 1e3, "refit_s": ms[1] / 1e3, "reduce_s": ms[2] / 1e3, "refit_kernel_ms": ms[1], "n_chunks": int(ms[3]),
-               "total_s": time.perf_counter() - t_start}
-    return NBGofResult(exposures=H, reconstruction_errors=err, n_iterations=nit, converged=conv.astype(bool), dispersion=alpha,
-                       log_likelihood=-err + nb_constant(X, alpha), n_exceed=exceed, p_value=(1 + exceed.astype(np.int64)) / (B + 1), null_mean=mean,
-                       null_errors=err_b, null_n_iterations=nit_b, draws=drawn, timings=timings)
+    fields, failed = call_gof("salnmf_nb_goodness_of_fit", (alpha,), X, S, B, seed, min_it, max_it, freq, tol, chunk, keep_draws, device, t_start,
+                              count_failed=True)
+    _failed_rows(failed, "nb_goodness_of_fit")
+    return NBGofResult(**fields, dispersion=alpha, log_likelihood=-fields["reconstruction_errors"] + nb_constant(X, alpha))
 
 
 def _cohort_profiles(cohorts, S, g, poisson: bool, it, device):
@@ -335,10 +275,9 @@ def _cohort_profiles(cohorts, S, g, poisson: bool, it, device):
     one after the other, in ONE negative-binomial launch, and one Poisson refit of the C N rows."""
     C, N, V = cohorts.shape
     A = g.size
-    q = np.empty(0)
     rows = np.ascontiguousarray(np.tile(cohorts[:, None], (1, A, 1, 1)).reshape(C * A * N, V))  # problem (c, a, n): sample n of cohort c at grid[a]
-    _, err, *_ = _call(rows, S, np.tile(np.repeat(g, N), C), 0, 0, q, *it, 0, False, device)
-    divergence = err.reshape(C, A, N)
+    fit = call_refit("salnmf_nb_refit_exposures", (np.tile(np.repeat(g, N), C),), rows, S, 0, 0, np.empty(0), *it, 0, False, device)
+    divergence = fit["reconstruction_errors"].reshape(C, A, N)
     profile = np.stack([[-divergence[c, a] + nb_constant(cohorts[c], np.full(N, g[a])) for a in range(A)] for c in range(C)])
     if not poisson:
         return profile, None
@@ -411,9 +350,7 @@ def dispersion_test(counts, signatures, grid=np.geomspace(1, 1e4, 17), n_draws: 
         H = est.exposures[best, np.arange(N)]  # every sample's exposures at the estimate
         draws, _ = estimates(draw_nb_counts(H, S, est.dispersion, B, seed, device=device), False)
         order = np.sort(draws, axis=0)
-        pos = np.asarray(q, dtype=np.float64) * (B - 1)
-        index = np.clip(np.where(np.asarray(q) <= 0.5, np.floor(pos), np.ceil(pos)).astype(np.int64), 0, B - 1)
-        res.dispersion_draws, res.dispersion_interval = draws, order[index]
+        res.dispersion_draws, res.dispersion_interval = draws, order[quantile_indices(q, B)]
         res.dispersion_bias = np.median(draws, axis=0) / est.dispersion
         if not per_sample:
             res.dispersion_bias = float(res.dispersion_bias)

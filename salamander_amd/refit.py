@@ -111,19 +111,11 @@ def check_arguments(counts, signatures, n_resamples, resample_seed, quantiles, m
     return X, S, R, seed, min_it, max_it, freq, tol, q, chunk
 
 
-def refit_exposures(counts, signatures, n_resamples: int = 0, resample_seed: int = 0, quantiles=(0.025, 0.5, 0.975),
-                    min_iterations: int = 500, max_iterations: int = 10000, conv_test_freq: int = 10, tol: float = 1e-7,
-                    keep_resamples: bool = False, device: int = 0, chunk_bytes: int | None = None) -> RefitResult:
-    """Exposures of every row of ``counts (N, V)`` to the fixed ``signatures (K, V)``, K <= 96 and V <= 96.
-
-    The signature rows are divided by their sums and used as they are (never clipped).  Every sample is iterated and
-    stopped on its own (module docstring); ``n_resamples`` adds the bootstrap: ``exposures_mean``, ``exposures_quantiles``
-    (existing values: index ``floor(q (R - 1))`` of the sorted resamples for q <= 0.5, ``ceil`` above) and, with
-    ``keep_resamples``, every resample's exposures.  ``chunk_bytes`` bounds the device buffer the resamples are drawn into
-    (default 256 MiB; the result does not depend on it).  Anything out of range is a ``ValueError`` before the device is touched."""
-    t_start = time.perf_counter()
-    X, S, R, seed, min_it, max_it, freq, tol, q, chunk = check_arguments(counts, signatures, n_resamples, resample_seed, quantiles, min_iterations,
-                                                                         max_iterations, conv_test_freq, tol, chunk_bytes)
+def call_refit(symbol, model_args, X, S, R, seed, q, min_it, max_it, freq, tol, chunk, keep_resamples, device, t_start=None) -> dict:
+    """One ``salnmf_*_refit_exposures`` call on checked arguments: the outputs' allocation, the call of ``symbol`` with
+    ``model_args`` (the model's own arrays) after K, and the timings (``total_s`` from ``t_start``, the caller's start).  Returns the
+    fields of a :class:`RefitResult`."""
+    t_start = time.perf_counter() if t_start is None else t_start
     (N, V), K = X.shape, S.shape[0]
     lib = _lib.load_with_device()
 
@@ -139,12 +131,28 @@ def refit_exposures(counts, signatures, n_resamples: int = 0, resample_seed: int
     Hr = np.empty((R, N, K), dtype=np.float64) if R and keep_resamples else None
     ms = (c_double * 4)()
     p = _lib.pointer
-    _lib.check(lib.salnmf_refit_exposures(
-        int(device), p(X), N, V, p(S), K, R, seed, Q if R else 0, p(q), min_it, max_it, freq, tol, chunk,
+    _lib.check(getattr(lib, symbol)(
+        int(device), p(X), N, V, p(S), K, *(p(m) for m in model_args), R, seed, Q if R else 0, p(q), min_it, max_it, freq, tol, chunk,
         p(H), p(err), p(nit), p(conv), p(Hq), p(Hm), p(nit_r), p(err_r), p(Hr), ctypes.cast(ms, _lib._D),
     ))
     timings = {"resample_s": ms[0] / 1e3, "refit_s": ms[1] / 1e3, "reduce_s": ms[2] / 1e3, "refit_kernel_ms": ms[1],
                "n_chunks": int(ms[3]), "total_s": time.perf_counter() - t_start}
-    return RefitResult(exposures=H, reconstruction_errors=err, n_iterations=nit, converged=conv.astype(bool), exposures_quantiles=Hq,
-                       exposures_mean=Hm, n_iterations_resampled=nit_r, reconstruction_errors_resampled=err_r, exposures_resampled=Hr,
-                       quantiles=tuple(float(v) for v in q), timings=timings)
+    return dict(exposures=H, reconstruction_errors=err, n_iterations=nit, converged=conv.astype(bool), exposures_quantiles=Hq,
+                exposures_mean=Hm, n_iterations_resampled=nit_r, reconstruction_errors_resampled=err_r, exposures_resampled=Hr,
+                quantiles=tuple(float(v) for v in q), timings=timings)
+
+
+def refit_exposures(counts, signatures, n_resamples: int = 0, resample_seed: int = 0, quantiles=(0.025, 0.5, 0.975),
+                    min_iterations: int = 500, max_iterations: int = 10000, conv_test_freq: int = 10, tol: float = 1e-7,
+                    keep_resamples: bool = False, device: int = 0, chunk_bytes: int | None = None) -> RefitResult:
+    """Exposures of every row of ``counts (N, V)`` to the fixed ``signatures (K, V)``, K <= 96 and V <= 96.
+
+    The signature rows are divided by their sums and used as they are (never clipped).  Every sample is iterated and
+    stopped on its own (module docstring); ``n_resamples`` adds the bootstrap: ``exposures_mean``, ``exposures_quantiles``
+    (existing values: index ``floor(q (R - 1))`` of the sorted resamples for q <= 0.5, ``ceil`` above) and, with
+    ``keep_resamples``, every resample's exposures.  ``chunk_bytes`` bounds the device buffer the resamples are drawn into
+    (default 256 MiB; the result does not depend on it).  Anything out of range is a ``ValueError`` before the device is touched."""
+    t_start = time.perf_counter()
+    X, S, R, seed, min_it, max_it, freq, tol, q, chunk = check_arguments(counts, signatures, n_resamples, resample_seed, quantiles, min_iterations,
+                                                                         max_iterations, conv_test_freq, tol, chunk_bytes)
+    return RefitResult(**call_refit("salnmf_refit_exposures", (), X, S, R, seed, q, min_it, max_it, freq, tol, chunk, keep_resamples, device, t_start))
