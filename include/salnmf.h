@@ -952,6 +952,33 @@ int salnmf_nb_goodness_of_fit(int device, const double* counts, int64_t n_sample
                               double* errors, int* n_iterations, int* converged, int* n_exceed, double* null_mean,
                               double* null_errors, int* null_n_iterations, double* draws, double* timings, int* n_failed);
 
+/* ---- sparse assignment under the negative-binomial likelihood.
+ *
+ * salnmf_assign_signatures_ex with the step and the divergence of salnmf_nb_refit_exposures: every argument and output means what
+ * it means there, `dispersion` holds one alpha per sample (a resample of sample n carries sample n's), errors / kl_increase /
+ * kl_decrease are negative-binomial divergences and their differences -- log-likelihood differences of one sample at one alpha,
+ * so max_kl_increase keeps its meaning.  Contract, for problem p (sample n or a resample of it), C_n the candidates (all K if
+ * null), R_n the required subset (none if null):
+ *   x = max(row, SALNMF_EPSILON);  h0 = (sum_v x_v) / |C_n|;  h = h0 on C_n and exactly 0.0 elsewhere;
+ *   a SOLVE iterates the entries that are not 0.0:  p = h W, a_v = x_v / p_v, b_v = (x_v + alpha) / (p_v + alpha),
+ *     un_k = sum_v W_kv a_v, ud_k = sum_v W_kv b_v, h_k <- max((h_k un_k) / ud_k, SALNMF_EPSILON); tested on the negative-binomial
+ *     divergence at iteration 0 and every multiple of conv_test_freq counted from the solve's start; the stop rule of section 14;
+ *   phase 0 solves on C_n (dense_*: with no sets, salnmf_nb_refit_exposures bit for bit); backward rounds as section 14 with the
+ *     protected set starting as R_n; with readd the re-addition pass of section 14.1, its selection factor u_k = un_k / ud_k at the
+ *     accepted h (one division; not the step's quantity), largest first, lowest index on equal values, tried only if u_k > 1.
+ * candidates = required = A is the solve on the active set A: no trial, exposures = dense_exposures.
+ * Refused (status 1, before any launch, nothing written): what salnmf_assign_signatures_ex refuses, a null dispersion, and a
+ * dispersion that is not finite or lies outside (0, 1e6]. */
+int salnmf_nb_assign_signatures(int device, const double* counts, int64_t n_samples, int n_features, const double* signatures,
+                                int n_signatures, const double* dispersion, int n_resamples, uint64_t seed, int n_quantiles,
+                                const double* quantiles, int min_iterations, int max_iterations, int conv_test_freq, double tol,
+                                double max_kl_increase, int64_t chunk_bytes, const uint8_t* candidates, const uint8_t* required, int readd,
+                                double* exposures, int* active, double* errors, int* removal_round, double* kl_increase, int* n_trials,
+                                int64_t* n_iterations, int* converged, double* dense_exposures, double* dense_errors,
+                                int* dense_n_iterations, int* dense_converged, double* selection_frequency, double* exposures_quantiles,
+                                double* exposures_mean, double* exposures_resampled, int* readd_round, double* kl_decrease,
+                                double* timings);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,8 +15,8 @@ from .covariance import CovarianceResult, exposure_covariance
 from .engine import Engine
 from .gof import GofResult, draw_model_counts, goodness_of_fit
 from .intervals import IntervalResult, ProfileResult, exposure_intervals, profile_likelihood
-from .nb import (DispersionResult, DispersionTestResult, NBGofResult, NBRefitResult, dispersion_test, draw_nb_counts, estimate_dispersion,
-                 nb_goodness_of_fit, nb_refit_exposures)
+from .nb import (DispersionResult, DispersionTestResult, NBAssignResult, NBGofResult, NBRefitResult, dispersion_test, draw_nb_counts,
+                 estimate_dispersion, nb_assign_signatures, nb_goodness_of_fit, nb_refit_exposures)
 from .power import PowerResult, signature_power
 from .presence import PresenceResult, signature_presence_test
 from .refit import RefitResult, refit_exposures
@@ -31,4 +31,5 @@ __all__ = ["models", "Engine", "AnnData", "MuData", "EngineUnavailable", "resamp
            "PresenceResult", "signature_power", "PowerResult", "profile_likelihood", "ProfileResult", "exposure_intervals", "IntervalResult",
            "exposure_covariance", "CovarianceResult", "exposure_change_test", "ChangeResult", "signature_change_test",
            "SignatureChangeResult", "nb_refit_exposures", "NBRefitResult", "estimate_dispersion", "DispersionResult",
-           "draw_nb_counts", "nb_goodness_of_fit", "NBGofResult", "dispersion_test", "DispersionTestResult"]
+           "draw_nb_counts", "nb_goodness_of_fit", "NBGofResult", "dispersion_test", "DispersionTestResult",
+           "nb_assign_signatures", "NBAssignResult"]

@@ -173,6 +173,10 @@ SIGNATURES = {
     "salnmf_draw_nb_counts": (c_int, [c_int, _D, c_int64, c_int, _D, c_int, _D, c_int, c_uint64, _D, _I]),
     "salnmf_nb_goodness_of_fit": (c_int, [c_int, _D, c_int64, c_int, _D, c_int, _D, c_int, c_uint64, c_int, c_int, c_int, c_double, c_int64,
                                           _D, _D, _I, _I, _I, _D, _D, _I, _D, _D, _I]),
+    # sparse assignment under the negative-binomial likelihood: salamander_amd/nb.py
+    "salnmf_nb_assign_signatures": (c_int, [c_int, _D, c_int64, c_int, _D, c_int, _D, c_int, c_uint64, c_int, _D, c_int, c_int, c_int, c_double, c_double,
+                                            c_int64, POINTER(c_uint8), POINTER(c_uint8), c_int,
+                                            _D, _I, _D, _I, _D, _I, POINTER(c_int64), _I, _D, _D, _I, _I, _D, _D, _D, _D, _I, _D, _D]),
 }
 
 OBJECTIVE_SLOTS = 256  # SALNMF_OBJECTIVE_SLOTS

@@ -98,15 +98,27 @@ def assign_signatures(counts, signatures, max_kl_increase: float = 1.92, n_resam
     t_start = time.perf_counter()
     X, S, R, seed, min_it, max_it, freq, tol, q, chunk = check_arguments(counts, signatures, n_resamples, resample_seed, quantiles, min_iterations,
                                                                          max_iterations, conv_test_freq, tol, chunk_bytes)
-    if max_it % freq != 0:
+    thr = check_threshold(max_it, freq, max_kl_increase)
+    C, Rq, readd = check_sets(candidates, required, readd, X.shape[0], S.shape[0])
+    return AssignResult(**call_assign("salnmf_assign_signatures_ex", (), X, S, R, seed, q, min_it, max_it, freq, tol, thr, chunk, C, Rq, readd,
+                                      keep_resamples, device, t_start))
+
+
+def check_threshold(max_iterations: int, conv_test_freq: int, max_kl_increase) -> float:
+    """``max_kl_increase`` as a float, or ``ValueError``: a finite number, and ``max_iterations`` a multiple of ``conv_test_freq``."""
+    if max_iterations % conv_test_freq != 0:
         raise ValueError("'max_iterations' must be a multiple of 'conv_test_freq': the solves of a sample follow one another on the device.")
     if isinstance(max_kl_increase, bool) or not isinstance(max_kl_increase, (int, float, np.integer, np.floating)) or not np.isfinite(max_kl_increase):
         raise ValueError("'max_kl_increase' must be a finite number.")
-    thr = float(max_kl_increase)
-    (N, V), K = X.shape, S.shape[0]
-    C, Rq, readd = check_sets(candidates, required, readd, N, K)
-    lib = _lib.load_with_device()
+    return float(max_kl_increase)
 
+
+def call_assign(symbol: str, model_args: tuple, X, S, R, seed, q, min_it, max_it, freq, tol, thr, chunk, C, Rq, readd, keep_resamples, device,
+                t_start) -> dict:
+    """One call of an assignment entry point (``salnmf_assign_signatures_ex``, or ``salnmf_nb_assign_signatures`` with the
+    dispersions as ``model_args``, which follow ``n_signatures``) on validated arguments: the fields of :class:`AssignResult`."""
+    (N, V), K = X.shape, S.shape[0]
+    lib = _lib.load_with_device()
     Q = int(q.size)
     f64 = lambda *shape: np.empty(shape, dtype=np.float64)  # noqa: E731
     i32 = lambda *shape: np.empty(shape, dtype=np.int32)  # noqa: E731
@@ -123,15 +135,15 @@ def assign_signatures(counts, signatures, max_kl_increase: float = 1.92, n_resam
     Rb = None if Rq is None else Rq.astype(np.uint8)
     ms = (c_double * 4)()
     p = _lib.pointer
-    _lib.check(lib.salnmf_assign_signatures_ex(
-        int(device), p(X), N, V, p(S), K, R, seed, Q if R else 0, p(q), min_it, max_it, freq, tol, thr, chunk, p(Cb), p(Rb), int(readd),
-        p(H), p(act), p(err), p(rnd), p(kl), p(ntr), p(nit), p(conv), p(Hd), p(err_d), p(nit_d), p(conv_d), p(sel), p(Hq), p(Hm), p(Hr),
-        p(rrnd), p(kld), ctypes.cast(ms, _lib._D),
+    _lib.check(getattr(lib, symbol)(
+        int(device), p(X), N, V, p(S), K, *(p(v) for v in model_args), R, seed, Q if R else 0, p(q), min_it, max_it, freq, tol, thr, chunk, p(Cb),
+        p(Rb), int(readd), p(H), p(act), p(err), p(rnd), p(kl), p(ntr), p(nit), p(conv), p(Hd), p(err_d), p(nit_d), p(conv_d), p(sel), p(Hq), p(Hm),
+        p(Hr), p(rrnd), p(kld), ctypes.cast(ms, _lib._D),
     ))
     timings = {"resample_s": ms[0] / 1e3, "assign_s": ms[1] / 1e3, "reduce_s": ms[2] / 1e3, "assign_kernel_ms": ms[1],
                "n_chunks": int(ms[3]), "total_s": time.perf_counter() - t_start}
-    return AssignResult(exposures=H, active=act.astype(bool), reconstruction_errors=err, removal_round=rnd, kl_increase=kl, n_trials=ntr,
-                        n_iterations=nit, converged=conv.astype(bool), dense_exposures=Hd, dense_errors=err_d, dense_n_iterations=nit_d,
-                        dense_converged=conv_d.astype(bool), selection_frequency=sel, exposures_quantiles=Hq, exposures_mean=Hm,
-                        exposures_resampled=Hr, quantiles=tuple(float(v) for v in q), max_kl_increase=thr, timings=timings, readd_round=rrnd,
-                        kl_decrease=kld, candidates=C, required=Rq)
+    return dict(exposures=H, active=act.astype(bool), reconstruction_errors=err, removal_round=rnd, kl_increase=kl, n_trials=ntr,
+                n_iterations=nit, converged=conv.astype(bool), dense_exposures=Hd, dense_errors=err_d, dense_n_iterations=nit_d,
+                dense_converged=conv_d.astype(bool), selection_frequency=sel, exposures_quantiles=Hq, exposures_mean=Hm,
+                exposures_resampled=Hr, quantiles=tuple(float(v) for v in q), max_kl_increase=thr, timings=timings, readd_round=rrnd,
+                kl_decrease=kld, candidates=C, required=Rq)

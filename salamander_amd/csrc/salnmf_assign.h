@@ -71,6 +71,9 @@ struct AssignSelectArgs {
     int R;
 };
 
+// salnmf_refit.hip (the translation unit of assign_selection_kernel): freq [NK] from the resamples' exposures H [R][NK]
+void assign_launch_selection(const double* H, double* freq, int64_t NK, int R, hipStream_t stream);
+
 #ifdef SALNMF_REFIT_KERNELS
 
 template <int KT, bool EX>
@@ -328,6 +331,10 @@ __global__ void __launch_bounds__(BLOCK) assign_kernel(AssignArgs a) {
     }
 }
 
+#endif  // SALNMF_REFIT_KERNELS
+
+#ifdef SALNMF_ASSIGN_SELECT_KERNEL  // salnmf_refit.hip alone: an ordinary kernel, defined once in the library (assign_launch_selection)
+
 // selection_frequency[n][k] = (resamples whose exposure of k in n is > 0) / R, counted in integers
 __global__ void __launch_bounds__(256) assign_selection_kernel(AssignSelectArgs a) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -336,6 +343,6 @@ __global__ void __launch_bounds__(256) assign_selection_kernel(AssignSelectArgs 
     for (int r = 0; r < a.R; ++r) c += a.H[(size_t)r * a.NK + i] > 0.0 ? 1 : 0;
     a.freq[i] = (double)c / (double)a.R;
 }
-#endif  // SALNMF_REFIT_KERNELS
+#endif  // SALNMF_ASSIGN_SELECT_KERNEL
 
 }  // namespace salnmf

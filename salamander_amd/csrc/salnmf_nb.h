@@ -37,7 +37,7 @@ struct NbRefitArgs {
     double tol;
 };
 
-#ifdef SALNMF_NB_KERNELS  // salnmf_nb.hip alone compiles the kernel (salnmf_kernels.h first, salnmf_refit.h's pieces enabled)
+#ifdef SALNMF_NB_KERNELS  // the units of the negative-binomial kernels (salnmf_kernels.h first, salnmf_refit.h's pieces enabled)
 
 __device__ __forceinline__ double nb_log(double x, double p) {
     return (log_operand_ok(x) && log_operand_ok(p)) ? log_ratio(x, p) : log(x / p);
@@ -60,6 +60,8 @@ __device__ __forceinline__ double nb_objective(const double (&x)[VT][4], const d
     }
     return rows_sum(acc);
 }
+
+#ifndef SALNMF_NB_PIECES_ONLY  // salnmf_nb_assign.hip takes nb_log and nb_objective above and leaves the kernel to salnmf_nb.hip
 
 template <int KT>
 __global__ void __launch_bounds__(BLOCK) nb_refit_kernel(NbRefitArgs a) {
@@ -153,6 +155,7 @@ __global__ void __launch_bounds__(BLOCK) nb_refit_kernel(NbRefitArgs a) {
         }
     }
 }
+#endif  // SALNMF_NB_PIECES_ONLY
 #endif  // SALNMF_NB_KERNELS
 
 }  // namespace salnmf

@@ -30,13 +30,6 @@ int launch_nb_refit(const NbRefitArgs& a, int cus, hipStream_t stream) {
                         [&](auto kt, dim3 grid) { hipLaunchKernelGGL(nb_refit_kernel<decltype(kt)::value>, grid, dim3(BLOCK), 0, stream, a); });
 }
 
-int nb_check_dispersion(const double* dispersion, int64_t N) {
-    for (int64_t n = 0; n < N; ++n)
-        if (!std::isfinite(dispersion[n]) || !(dispersion[n] > 0.0) || dispersion[n] > NB_ALPHA_MAX)
-            return fail("dispersion must be finite and in (0, %g]: sample %lld holds %g", NB_ALPHA_MAX, (long long)n, dispersion[n]);
-    return 0;
-}
-
 // A problem list of `copies` resamples (draws) of the samples reads the samples' dispersions repeated `copies` times: a copy of
 // sample n carries sample n's dispersion
 std::vector<double> nb_tile_dispersion(const double* dispersion, int64_t N, int copies) {

@@ -11,11 +11,12 @@
 // the per-signature test of a changed share (salnmf_signature_change; salnmf_sigchange.h: sigchange_kernel here, sigchange_draw_kernel in
 // salnmf_batch.hip), DESIGN.md section 22.  The six tile-solve kernels share the solve_* pieces of salnmf_refit.h; the drivers below share one kit:
 // from salnmf_host_kit.h launch_tiles, the argument checks, Spans, chunk_rows and upload / download; from salnmf_refit_drivers.h
-// bootstrap_refit, gof_run and draw_run, which the negative-binomial entry points of salnmf_nb.hip call too; refit_launch_reduce
-// here, next to its kernel; and for the pair calls pair_observed and pair_draw_solve.
+// refit_prepare, bootstrap_refit, gof_run, draw_run and assign_run, which the negative-binomial entry points of salnmf_nb.hip and
+// salnmf_nb_assign.hip call too; refit_launch_reduce and assign_launch_selection here, next to their kernels; and for the pair calls pair_observed and pair_draw_solve.
 #define SALNMF_TEMPLATES_ONLY 1
 #define SALNMF_REFIT_KERNELS 1
 #define SALNMF_REFIT_REDUCE_KERNEL 1
+#define SALNMF_ASSIGN_SELECT_KERNEL 1
 #include "../../include/salnmf.h"
 #include "salnmf_kernels.h"
 #include "salnmf_device.h"
@@ -38,61 +39,6 @@
 using namespace salnmf;
 
 namespace {
-
-// What the refit, the assignment, the goodness-of-fit test and the pair calls check and prepare before any launch: the checks of
-// salnmf_host_kit.h in their order, with the assignment's sets between the ranges and the signatures, then the device and its CU count.
-struct RefitInputs {
-    std::vector<double> x;
-    std::vector<uint32_t> icounts;
-    std::vector<uint32_t> cand, req;  // the assignment's sets as [N][words] bit masks; empty where the argument is null
-    RefitReduceArgs red{};
-    int cus = 0;
-};
-
-// The assignment's optional sets: one byte per (sample, signature), anything but 0 is "set".
-struct AssignSets {
-    const uint8_t* candidates = nullptr;
-    const uint8_t* required = nullptr;
-    int readd = 0;
-};
-
-int refit_prepare(int device, const double* counts, int64_t N, int V, const double* signatures, int K, int R, int Q, const double* quantiles,
-                  int min_iterations, int max_iterations, int conv_test_freq, double tol, bool resample_outputs, RefitInputs& in,
-                  const AssignSets& sets = AssignSets{}) {
-    CK(check_refit_ranges(N, V, K, R, min_iterations, max_iterations, conv_test_freq, tol, Q, resample_outputs));
-    if (sets.readd != 0 && sets.readd != 1) return fail("readd must be 0 or 1, got %d", sets.readd);
-    const int words = ((K + 15) / 16 + 1) / 2;  // assign_kernel<KT>: NW
-    auto pack = [&](const uint8_t* set, std::vector<uint32_t>& out) {
-        out.assign((size_t)N * words, 0u);
-        for (int64_t n = 0; n < N; ++n)
-            for (int k = 0; k < K; ++k)
-                if (set[(size_t)n * K + k]) out[(size_t)n * words + (k >> 5)] |= 1u << (k & 31);
-    };
-    if (sets.candidates) {
-        pack(sets.candidates, in.cand);
-        for (int64_t n = 0; n < N; ++n) {
-            uint32_t any = 0u;
-            for (int w = 0; w < words; ++w) any |= in.cand[(size_t)n * words + w];
-            if (!any) return fail("sample %lld has no candidate signature", (long long)n);
-        }
-    }
-    if (sets.required) {
-        pack(sets.required, in.req);
-        if (sets.candidates)
-            for (size_t i = 0; i < in.req.size(); ++i)
-                if (in.req[i] & ~in.cand[i]) {
-                    const uint32_t off = in.req[i] & ~in.cand[i];
-                    return fail("sample %lld: required signature %d is not a candidate", (long long)(i / words), 32 * (int)(i % words) + __builtin_ctz(off));
-                }
-    }
-    CK(check_signatures(signatures, K, V));
-    CK(clip_counts(counts, N, V, in.x));
-    if (R > 0) CK(check_resamples(counts, N, V, R, Q, quantiles, in.icounts, in.red.index));
-    hipDeviceProp_t prop;
-    CK(open_device(device, &prop));
-    in.cus = prop.multiProcessorCount;
-    return 0;
-}
 
 // ---- the launchers of the tile-solve kernels (salnmf_host_kit.h: launch_tiles)
 
@@ -128,6 +74,11 @@ void salnmf::refit_launch_reduce(RefitReduceArgs& red, const double* H, double* 
     red.R2 = 1;
     while (red.R2 < R) red.R2 <<= 1;
     hipLaunchKernelGGL(refit_reduce_kernel, dim3((unsigned)N), dim3(REFIT_SORT_BLOCK), 0, stream, red);
+}
+
+void salnmf::assign_launch_selection(const double* H, double* freq, int64_t NK, int R, hipStream_t stream) {
+    const AssignSelectArgs sel{H, freq, NK, R};
+    hipLaunchKernelGGL(assign_selection_kernel, dim3((unsigned)((NK + 255) / 256)), dim3(256), 0, stream, sel);
 }
 
 extern "C" int salnmf_refit_exposures(int device, const double* counts, int64_t n_samples, int n_features, const double* signatures, int n_signatures,
@@ -176,126 +127,21 @@ extern "C" int salnmf_assign_signatures_ex(int device, const double* counts, int
                                            double* exposures_resampled, int* readd_round, double* kl_decrease, double* timings) {
     const int64_t N = n_samples;
     const int V = n_features, K = n_signatures, R = n_resamples, Q = n_quantiles;
-    if (!counts || !signatures || !exposures || !active || !errors || !removal_round || !kl_increase || !n_trials || !n_iterations || !converged ||
-        !dense_exposures || !dense_errors || !dense_n_iterations || !dense_converged)
-        return fail("null argument");
-    if (readd == 1 && (!readd_round || !kl_decrease)) return fail("null output for the re-addition pass");
-    if (!std::isfinite(max_kl_increase)) return fail("max_kl_increase must be finite, got %g", max_kl_increase);
-    // (solves follow one another inside one wave, and the tests of its 16 problems must fall on the same iterations)
-    if (conv_test_freq >= 1 && max_iterations >= 0 && max_iterations % conv_test_freq != 0)
-        return fail("max_iterations must be a multiple of conv_test_freq, got %d and %d", max_iterations, conv_test_freq);
+    const AssignOutputs out{exposures, active, errors, removal_round, kl_increase, n_trials, n_iterations, converged, dense_exposures, dense_errors,
+                            dense_n_iterations, dense_converged, selection_frequency, exposures_quantiles, exposures_mean, exposures_resampled, readd_round,
+                            kl_decrease, timings};
+    CK(assign_check(out, counts && signatures, readd, max_kl_increase, max_iterations, conv_test_freq));
     RefitInputs in;
     CK(refit_prepare(device, counts, N, V, signatures, K, R, Q, quantiles, min_iterations, max_iterations, conv_test_freq, tol,
                      selection_frequency && exposures_mean && (Q <= 0 || (quantiles && exposures_quantiles)), in, AssignSets{candidates, required, readd}));
-    const int cus = in.cus;
-    const int chunk = bootstrap_chunk(chunk_bytes, N, V, R);
-
     DevBufs d;
     CK(d.own_stream());
-    const size_t NK = (size_t)N * K, NR = (size_t)N * (size_t)std::max(R, 1);
     double* dW = upload(d, signatures, (size_t)K * V);
     double* dX = upload(d, in.x);
-    double* dH = d.get<double>(NK);
-    double* dHd = d.get<double>(NK);
-    double* dkl = d.get<double>(NK);
-    int* dact = d.get<int>(NK);
-    int* dround = d.get<int>(NK);
-    double* derr = d.get<double>((size_t)N);
-    double* derr_d = d.get<double>((size_t)N);
-    long long* dnit = d.get<long long>((size_t)N);
-    int* dconv = d.get<int>((size_t)N);
-    int* dntr = d.get<int>((size_t)N);
-    int* dnit_d = d.get<int>((size_t)N);
-    int* dconv_d = d.get<int>((size_t)N);
-    unsigned* dnext = d.get<unsigned>(1);
-    if (!dW || !dX || !dH || !dHd || !dkl || !dact || !dround || !derr || !derr_d || !dnit || !dconv || !dntr || !dnit_d || !dconv_d || !dnext)
-        return fail("hipMalloc failed (assignment of %lld samples)", (long long)N);
-    uint32_t *dcand = nullptr, *dreq = nullptr;
-    int* drround = nullptr;
-    double* dkld = nullptr;
-    if (candidates) dcand = upload(d, in.cand);
-    if (required) dreq = upload(d, in.req);
-    if (readd) drround = d.get<int>(NK), dkld = d.get<double>(NK);
-    if ((candidates && !dcand) || (required && !dreq) || (readd && (!drround || !dkld))) return fail("hipMalloc failed (sets of %lld samples)", (long long)N);
-    uint32_t* dcounts = nullptr;
-    double *dXr = nullptr, *dHr = nullptr, *derr_r = nullptr, *dquant = nullptr, *dmean = nullptr, *dfreq = nullptr;
-    long long* dnit_r = nullptr;
-    int *dconv_r = nullptr, *dntr_r = nullptr;
-    if (R > 0) {
-        dcounts = upload(d, in.icounts);
-        dXr = d.get<double>((size_t)chunk * N * V);
-        dHr = d.get<double>(NR * K);
-        derr_r = d.get<double>(NR);
-        dnit_r = d.get<long long>(NR);
-        dconv_r = d.get<int>(NR);
-        dntr_r = d.get<int>(NR);
-        dquant = d.get<double>((size_t)std::max(Q, 1) * NK);
-        dmean = d.get<double>(NK);
-        dfreq = d.get<double>(NK);
-        if (!dcounts || !dXr || !dHr || !derr_r || !dnit_r || !dconv_r || !dntr_r || !dquant || !dmean || !dfreq)
-            return fail("hipMalloc failed (%d resamples of %lld x %d, %d signatures)", R, (long long)N, V, K);
-    }
-
-    AssignArgs a{dX, dW, dH, derr, dnit, dconv, dntr, dact, dround, dkl, dHd, derr_d, dnit_d, dconv_d, dnext, N, V, K,
-                 min_iterations, max_iterations, conv_test_freq, tol, max_kl_increase, dcand, dreq, drround, dkld, N, readd};
-    Spans sp;  // resample, assign, reduce
-    sp.start(d, timings != nullptr);
-    CK(sp.timed(1, [&] { return launch_assign(a, cus, d.stream); }));
-    int n_chunks = 0;
-    for (int first = 0; first < R; first += chunk, ++n_chunks) {
-        const int count = std::min(chunk, R - first);
-        CK(sp.timed(0, [&]() -> int {
-            refit_launch_resample(dcounts, dXr, N, V, seed, first, count, d.stream);
-            HIPCK(hipGetLastError());
-            return 0;
-        }));
-        // a resample's problems keep their exposures only: no per-signature record, no phase-0 copy
-        AssignArgs c = a;
-        c.X = dXr;
-        c.P = (int64_t)count * N;
-        c.H = dHr + (size_t)first * NK;
-        c.err = derr_r + (size_t)first * N;
-        c.nit = dnit_r + (size_t)first * N;
-        c.conv = dconv_r + (size_t)first * N;
-        c.ntrials = dntr_r + (size_t)first * N;
-        c.active = nullptr, c.round = nullptr, c.kl = nullptr, c.rround = nullptr, c.kld = nullptr;
-        c.dH = nullptr, c.derr = nullptr, c.dnit = nullptr, c.dconv = nullptr;
-        CK(sp.timed(1, [&] { return launch_assign(c, cus, d.stream); }));
-    }
-    if (R > 0) {
-        const AssignSelectArgs sel{dHr, dfreq, (int64_t)NK, R};
-        CK(sp.timed(2, [&]() -> int {
-            refit_launch_reduce(in.red, dHr, dquant, dmean, N, K, R, Q, d.stream);
-            HIPCK(hipGetLastError());
-            hipLaunchKernelGGL(assign_selection_kernel, dim3((unsigned)((NK + 255) / 256)), dim3(256), 0, d.stream, sel);
-            HIPCK(hipGetLastError());
-            return 0;
-        }));
-        if (Q > 0) CK(download(d, exposures_quantiles, dquant, (size_t)Q * NK));
-        CK(download(d, exposures_mean, dmean, NK));
-        CK(download(d, selection_frequency, dfreq, NK));
-        if (exposures_resampled) CK(download(d, exposures_resampled, dHr, NR * K));
-    }
-    CK(download(d, exposures, dH, NK));
-    CK(download(d, active, dact, NK));
-    CK(download(d, removal_round, dround, NK));
-    CK(download(d, kl_increase, dkl, NK));
-    if (readd) {
-        CK(download(d, readd_round, drround, NK));
-        CK(download(d, kl_decrease, dkld, NK));
-    }
-    CK(download(d, errors, derr, (size_t)N));
-    CK(download(d, n_trials, dntr, (size_t)N));
-    CK(download(d, n_iterations, dnit, (size_t)N));
-    CK(download(d, converged, dconv, (size_t)N));
-    CK(download(d, dense_exposures, dHd, NK));
-    CK(download(d, dense_errors, derr_d, (size_t)N));
-    CK(download(d, dense_n_iterations, dnit_d, (size_t)N));
-    CK(download(d, dense_converged, dconv_d, (size_t)N));
-    HIPCK(hipStreamSynchronize(d.stream));
-    CK(sp.totals(3, timings));
-    if (timings) timings[3] = (double)n_chunks;
-    return 0;
+    AssignArgs a{};
+    a.X = dX, a.W = dW, a.P = N, a.V = V, a.K = K;
+    a.min_it = min_iterations, a.max_it = max_iterations, a.freq = conv_test_freq, a.tol = tol, a.thr = max_kl_increase, a.readd = readd;
+    return assign_run(d, dW && dX, a, in, R, Q, seed, chunk_bytes, out, launch_assign);
 }
 
 // ---- goodness of fit by parametric bootstrap (salnmf_gof.h)

@@ -10,7 +10,10 @@ Pelizzola et al. 2023), every sample iterated and stopped on its own, with a dis
 negative binomial is needed at all.  :func:`draw_nb_counts` draws count vectors from a fitted negative-binomial model on the
 device (``csrc/salnmf_nbdraw.h``), :func:`nb_goodness_of_fit` is the parametric-bootstrap test of
 :func:`goodness_of_fit <salamander_amd.gof.goodness_of_fit>` under that model, and :func:`dispersion_test` calibrates the
-dispersion estimate: a p-value for ``lr_statistic`` and an interval for the estimate.  There is no CPU fallback.
+dispersion estimate: a p-value for ``lr_statistic`` and an interval for the estimate.  :func:`nb_assign_signatures` is
+:func:`assign_signatures <salamander_amd.assign.assign_signatures>` under the negative-binomial model (``csrc/salnmf_nb_assign.h``,
+DESIGN.md section 25): which signatures are active in each sample, with candidate sets, required signatures and the re-addition
+pass.  There is no CPU fallback.
 """
 
 from __future__ import annotations
@@ -21,6 +24,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
+from .assign import AssignResult, assign_signatures, call_assign, check_sets, check_threshold
 from .gof import GofResult, call_gof, check_integer_counts, check_model, check_n_draws, draw_model_counts
 from .refit import RefitResult, call_refit, check_arguments, quantile_indices, refit_exposures
 from .resample import check_seed
@@ -126,6 +130,46 @@ def nb_refit_exposures(counts, signatures, dispersion, n_resamples: int = 0, res
     return NBRefitResult(**fit, dispersion=alpha, log_likelihood=-fit["reconstruction_errors"] + nb_constant(X, alpha))
 
 
+@dataclass
+class NBAssignResult(AssignResult):
+    """:class:`AssignResult <salamander_amd.assign.AssignResult>` with ``reconstruction_errors``, ``dense_errors``, ``kl_increase``
+    and ``kl_decrease`` holding negative-binomial divergences and their differences, plus the dispersions used and the samples'
+    log-likelihoods at the sparse and at the phase-0 exposures."""
+
+    dispersion: np.ndarray | None = None  # (N,)
+    log_likelihood: np.ndarray | None = None  # (N,): -reconstruction_errors + nb_constant(counts, dispersion)
+    dense_log_likelihood: np.ndarray | None = None  # (N,): -dense_errors + nb_constant(counts, dispersion)
+
+
+def nb_assign_signatures(counts, signatures, dispersion, max_kl_increase: float = 1.92, n_resamples: int = 0, resample_seed: int = 0,
+                         quantiles=(0.025, 0.5, 0.975), min_iterations: int = 500, max_iterations: int = 10000, conv_test_freq: int = 10,
+                         tol: float = 1e-7, keep_resamples: bool = False, device: int = 0, chunk_bytes: int | None = None,
+                         candidates=None, required=None, readd: bool = False) -> NBAssignResult:
+    """Sparse negative-binomial exposures of every row of ``counts (N, V)`` to the fixed ``signatures (K, V)``, K <= 96 and V <= 96.
+
+    :func:`assign_signatures <salamander_amd.assign.assign_signatures>` with the step and the divergence of
+    :func:`nb_refit_exposures`: phase 0 on the candidate set (with no sets, ``nb_refit_exposures`` bit for bit), backward
+    elimination of the active, unprotected signature of smallest exposure, and with ``readd=True`` the re-addition pass, all in
+    one kernel launch.  ``dispersion`` is a scalar or one value per sample, in (0, 1e6]; a resample carries its sample's.  The
+    difference of two negative-binomial divergences of one sample at one dispersion is a log-likelihood difference, so
+    ``max_kl_increase = 1.92`` keeps its meaning: half the 95 % point of a chi-square with one degree of freedom.  The
+    re-addition pass ranks the removed candidates by ``u_k = sum_v W_kv a_v / sum_v W_kv b_v`` at the accepted exposures
+    (``a = x / p``, ``b = (x + alpha) / (p + alpha)``) and tries those with ``u_k > 1``.  ``candidates = required = A`` is the solve
+    on the active set A: no trial, ``exposures == dense_exposures``, exactly 0.0 off A.  ``max_iterations`` must be a multiple
+    of ``conv_test_freq``.  Anything out of range is a ``ValueError`` before the device is touched."""
+    t_start = time.perf_counter()
+    X, S, R, seed, min_it, max_it, freq, tol, q, chunk = check_arguments(counts, signatures, n_resamples, resample_seed, quantiles, min_iterations,
+                                                                         max_iterations, conv_test_freq, tol, chunk_bytes)
+    alpha = check_dispersion(dispersion, X.shape[0])
+    thr = check_threshold(max_it, freq, max_kl_increase)
+    C, Rq, readd = check_sets(candidates, required, readd, X.shape[0], S.shape[0])
+    fit = call_assign("salnmf_nb_assign_signatures", (alpha,), X, S, R, seed, q, min_it, max_it, freq, tol, thr, chunk, C, Rq, readd, keep_resamples,
+                      device, t_start)
+    const = nb_constant(X, alpha)
+    return NBAssignResult(**fit, dispersion=alpha, log_likelihood=-fit["reconstruction_errors"] + const,
+                          dense_log_likelihood=-fit["dense_errors"] + const)
+
+
 def select_dispersion(grid, profile, poisson_log_likelihood, per_sample: bool = False):
     """``(dispersion, at_upper_edge, lr_statistic)`` of a profile ``(A, N)``: the first grid value of largest cohort sum (or of
     each sample's own column), whether it is the last one, and twice the log-likelihood gained over the Poisson fit."""
@@ -140,7 +184,8 @@ def select_dispersion(grid, profile, poisson_log_likelihood, per_sample: bool = 
 
 
 def estimate_dispersion(counts, signatures, grid=np.geomspace(1, 1e4, 17), per_sample: bool = False, min_iterations: int = 500,
-                        max_iterations: int = 10000, conv_test_freq: int = 10, tol: float = 1e-7, device: int = 0) -> DispersionResult:
+                        max_iterations: int = 10000, conv_test_freq: int = 10, tol: float = 1e-7, device: int = 0,
+                        candidates=None) -> DispersionResult:
     """The dispersion ``alpha`` of largest negative-binomial likelihood on a grid, for the cohort or per sample.
 
     Every sample is refitted at every grid value -- ``A x N`` problems in one list through one kernel launch, each carrying its
@@ -165,7 +210,11 @@ def estimate_dispersion(counts, signatures, grid=np.geomspace(1, 1e4, 17), per_s
     96    96    1e4 (top of the grid)
     ====  ====  ==================================
 
-    so estimate on the candidate set you will fit with, not on the whole catalogue."""
+    so estimate on the candidate set you will fit with, not on the whole catalogue: ``candidates`` is ``None`` or a boolean mask of
+    shape (K,) or (N, K), the signatures each sample may use.  With a mask every one of the ``A x N`` problems is solved on its
+    sample's set (:func:`nb_assign_signatures` with ``candidates = required =`` the mask: one solve, no trial), the Poisson fit is
+    ``assign_signatures(candidates=mask, required=mask)``, ``exposures`` are exactly 0.0 off the set, and ``max_iterations`` must be
+    a multiple of ``conv_test_freq``.  With ``None`` the call is what it was, bit for bit."""
     t_start = time.perf_counter()
     X, S, _, _, min_it, max_it, freq, tol, q, chunk = check_arguments(counts, signatures, 0, 0, (), min_iterations, max_iterations, conv_test_freq,
                                                                       tol, None)
@@ -173,6 +222,8 @@ def estimate_dispersion(counts, signatures, grid=np.geomspace(1, 1e4, 17), per_s
     (N, V), K, A = X.shape, S.shape[0], g.size
     if A * N >= 2**31:
         raise ValueError(f"{A} grid values x {N} samples: at most 2**31 - 1 problems.")
+    if candidates is not None:
+        return _estimate_on_sets(X, S, g, per_sample, min_it, max_it, freq, tol, q, chunk, device, candidates, t_start)
     # problem (a, n) is row a N + n of the list: sample n at grid[a]
     fit = call_refit("salnmf_nb_refit_exposures", (np.repeat(g, N),), np.ascontiguousarray(np.tile(X, (A, 1))), S, 0, 0, q, min_it, max_it, freq, tol,
                      chunk, False, device)
@@ -186,6 +237,27 @@ def estimate_dispersion(counts, signatures, grid=np.geomspace(1, 1e4, 17), per_s
     return DispersionResult(grid=g, profile=profile, dispersion=dispersion, at_upper_edge=edge, poisson_log_likelihood=poisson_ll, lr_statistic=lr,
                             exposures=H.reshape(A, N, K), divergence=divergence, n_iterations=nit.reshape(A, N), converged=conv.reshape(A, N),
                             timings=timings)
+
+
+def _estimate_on_sets(X, S, g, per_sample, min_it, max_it, freq, tol, q, chunk, device, candidates, t_start) -> DispersionResult:
+    """:func:`estimate_dispersion` with a candidate mask: the same problem list, every problem solved on its sample's set."""
+    (N, V), K, A = X.shape, S.shape[0], g.size
+    thr = check_threshold(max_it, freq, 0.0)
+    C, _, _ = check_sets(candidates, None, False, N, K)
+    tiled = np.ascontiguousarray(np.tile(C, (A, 1)))  # problem (a, n) is row a N + n: sample n at grid[a], on C_n
+    fit = call_assign("salnmf_nb_assign_signatures", (np.repeat(g, N),), np.ascontiguousarray(np.tile(X, (A, 1))), S, 0, 0, q, min_it, max_it, freq,
+                      tol, thr, chunk, tiled, tiled, False, False, device, time.perf_counter())
+    ms = fit["timings"]["assign_kernel_ms"]
+    divergence = fit["reconstruction_errors"].reshape(A, N)
+    profile = np.stack([-divergence[a] + nb_constant(X, np.full(N, g[a])) for a in range(A)])
+    poisson = assign_signatures(X, S, min_iterations=min_it, max_iterations=max_it, conv_test_freq=freq, tol=tol, device=device, candidates=C,
+                                required=C)
+    poisson_ll = -poisson.reconstruction_errors + poisson_constant(X)
+    dispersion, edge, lr = select_dispersion(g, profile, poisson_ll, per_sample)
+    timings = {"refit_s": ms / 1e3, "refit_kernel_ms": ms, "poisson_refit_s": poisson.timings["assign_s"], "total_s": time.perf_counter() - t_start}
+    return DispersionResult(grid=g, profile=profile, dispersion=dispersion, at_upper_edge=edge, poisson_log_likelihood=poisson_ll, lr_statistic=lr,
+                            exposures=fit["exposures"].reshape(A, N, K), divergence=divergence,
+                            n_iterations=fit["n_iterations"].astype(np.int32).reshape(A, N), converged=fit["converged"].reshape(A, N), timings=timings)
 
 
 @dataclass
