@@ -979,6 +979,33 @@ int salnmf_nb_assign_signatures(int device, const double* counts, int64_t n_samp
                                 double* exposures_mean, double* exposures_resampled, int* readd_round, double* kl_decrease,
                                 double* timings);
 
+/* ---- Is signature s present in this sample, under the negative-binomial model?  (csrc/salnmf_nb_presence.h)
+ * salnmf_signature_presence with the step and the divergence of salnmf_nb_refit_exposures and the draw of salnmf_draw_nb_counts:
+ * every argument and output means what it means there, `dispersion` holds one alpha per sample.  Contract, for sample n with
+ * alpha_n, candidate set C_n and s = test[j]:
+ *   a SOLVE ON A SET A is salnmf_nb_assign_signatures with candidates = required = A, bit for bit: exposures, error, iteration
+ *   count and convergence flag;
+ *   the alternative is the solve on C_n (h1, f1), the null the solve on C_n \ {s} (h0, f0); statistic[n, j] = f0 - f1, one rounded
+ *   subtraction of two negative-binomial divergences at alpha_n: a log-likelihood difference, half the likelihood-ratio statistic;
+ *   UNTESTED pairs as salnmf_signature_presence;
+ *   null draw b of the pair is one draw of salnmf_draw_nb_counts' contract from the exposures h0 and alpha_n, with the Philox
+ *   counter (q, 0x4E420000 + stream, n, ((s + 1) << 16) | b): b < 65536 fills the low half of the draw word and s + 1 the bits
+ *   above, so no pair's draws coincide with another's or with salnmf_draw_nb_counts' / salnmf_nb_goodness_of_fit's (upper half 0);
+ *   they depend on (seed, n, s, b), h0 and alpha_n only.  The draw is UNCONDITIONAL: null totals vary, as in
+ *   salnmf_nb_goodness_of_fit, written as max(count, SALNMF_EPSILON);
+ *   every draw goes through the same two solves from cold starts with alpha_n; the reduction is salnmf_signature_presence's.
+ * n_failed as salnmf_draw_nb_counts'.  timings as salnmf_signature_presence's.
+ * Refused, status 1 and salnmf_last_error: what salnmf_signature_presence refuses; a null dispersion or n_failed; a dispersion
+ * that is not finite or lies outside (0, 1e6] (all of these before any launch); and, after the observed launch and before any draw,
+ * a null fit h0 with sum_v (h0 W)_v above 2^24. */
+int salnmf_nb_signature_presence(int device, const double* counts, int64_t n_samples, int n_features, const double* signatures,
+                                 int n_signatures, const double* dispersion, const int* test, int n_test, const uint8_t* candidates,
+                                 int n_draws, uint64_t seed, int min_iterations, int max_iterations, int conv_test_freq, double tol,
+                                 int64_t chunk_bytes, uint8_t* tested, double* statistic, int* n_exceed, double* null_mean,
+                                 double* exposures, double* errors, double* null_exposures, double* null_errors, int* n_iterations,
+                                 int* converged, double* null_statistics, int* null_n_iterations, double* draws, double* timings,
+                                 int* n_failed);
+
 #ifdef __cplusplus
 }
 #endif

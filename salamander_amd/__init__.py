@@ -15,8 +15,8 @@ from .covariance import CovarianceResult, exposure_covariance
 from .engine import Engine
 from .gof import GofResult, draw_model_counts, goodness_of_fit
 from .intervals import IntervalResult, ProfileResult, exposure_intervals, profile_likelihood
-from .nb import (DispersionResult, DispersionTestResult, NBAssignResult, NBGofResult, NBRefitResult, dispersion_test, draw_nb_counts,
-                 estimate_dispersion, nb_assign_signatures, nb_goodness_of_fit, nb_refit_exposures)
+from .nb import (DispersionResult, DispersionTestResult, NBAssignResult, NBGofResult, NBPresenceResult, NBRefitResult, dispersion_test,
+                 draw_nb_counts, estimate_dispersion, nb_assign_signatures, nb_goodness_of_fit, nb_refit_exposures, nb_signature_presence_test)
 from .power import PowerResult, signature_power
 from .presence import PresenceResult, signature_presence_test
 from .refit import RefitResult, refit_exposures
@@ -32,4 +32,4 @@ __all__ = ["models", "Engine", "AnnData", "MuData", "EngineUnavailable", "resamp
            "exposure_covariance", "CovarianceResult", "exposure_change_test", "ChangeResult", "signature_change_test",
            "SignatureChangeResult", "nb_refit_exposures", "NBRefitResult", "estimate_dispersion", "DispersionResult",
            "draw_nb_counts", "nb_goodness_of_fit", "NBGofResult", "dispersion_test", "DispersionTestResult",
-           "nb_assign_signatures", "NBAssignResult"]
+           "nb_assign_signatures", "NBAssignResult", "nb_signature_presence_test", "NBPresenceResult"]

@@ -177,6 +177,9 @@ SIGNATURES = {
     "salnmf_nb_assign_signatures": (c_int, [c_int, _D, c_int64, c_int, _D, c_int, _D, c_int, c_uint64, c_int, _D, c_int, c_int, c_int, c_double, c_double,
                                             c_int64, POINTER(c_uint8), POINTER(c_uint8), c_int,
                                             _D, _I, _D, _I, _D, _I, POINTER(c_int64), _I, _D, _D, _I, _I, _D, _D, _D, _D, _I, _D, _D]),
+    # presence of single signatures under the negative-binomial model: salamander_amd/nb.py
+    "salnmf_nb_signature_presence": (c_int, [c_int, _D, c_int64, c_int, _D, c_int, _D, _I, c_int, POINTER(c_uint8), c_int, c_uint64, c_int, c_int, c_int,
+                                             c_double, c_int64, POINTER(c_uint8), _D, _I, _D, _D, _D, _D, _D, _I, _I, _D, _I, _D, _D, _I]),
 }
 
 OBJECTIVE_SLOTS = 256  # SALNMF_OBJECTIVE_SLOTS

@@ -16,6 +16,7 @@
 #define SALNMF_NBDRAW_KERNELS 1
 #include "salnmf_nbdraw.h"
 #include "salnmf_presence.h"
+#include "salnmf_nb_presence.h"
 #include "salnmf_change.h"
 #include "salnmf_sigchange.h"
 #include "salnmf_power.h"
@@ -353,6 +354,18 @@ void salnmf::presence_launch_draw(const double* H0, const double* W, const doubl
         const PresenceDrawArgs a{H0, W, X, pair_n, pair_s, out + (size_t)done * NP * V, NP, V, K, (uint32_t)seed, (uint32_t)(seed >> 32), floor,
                                  (uint32_t)(first + done)};
         hipLaunchKernelGGL(presence_draw_kernel, dim3((unsigned)NP, (unsigned)now), dim3(RESAMPLE_BLOCK), 0, stream, a);
+    }
+}
+
+// the negative-binomial presence test's draw (salnmf_nb_presence.h): nb_draw_kernel's body, one workgroup per (pair, draw)
+void salnmf::nb_presence_launch_draw(const double* H0, const double* W, const double* alpha, const double* gd, const double* gc, const int* pair_n,
+                                     const int* pair_s, double* out, unsigned* failed, int64_t NP, int V, int K, uint64_t seed, double floor, int first,
+                                     int count, hipStream_t stream) {
+    for (int done = 0; done < count; done += GOF_GRID_Y) {
+        const int now = std::min(GOF_GRID_Y, count - done);
+        const NbPresenceDrawArgs a{H0, W, alpha, gd, gc, pair_n, pair_s, out + (size_t)done * NP * V, failed, NP, V, K, (uint32_t)seed,
+                                   (uint32_t)(seed >> 32), floor, (uint32_t)(first + done)};
+        hipLaunchKernelGGL(nb_presence_draw_kernel, dim3((unsigned)NP, (unsigned)now), dim3(RESAMPLE_BLOCK), 0, stream, a);
     }
 }
 

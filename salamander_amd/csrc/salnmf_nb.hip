@@ -38,17 +38,6 @@ std::vector<double> nb_tile_dispersion(const double* dispersion, int64_t N, int 
     return alpha;
 }
 
-// The per-sample constants of the gamma draw (salnmf_nbdraw.h): d = a' - 1/3 and c = 1 / sqrt(9 d), a' = alpha (alpha >= 1) or alpha + 1:
-// computed here, so that the kernel's gamma path has no square root of its own
-void nb_gamma_constants(const double* dispersion, int64_t N, std::vector<double>& gd, std::vector<double>& gc) {
-    gd.resize((size_t)N), gc.resize((size_t)N);
-    for (int64_t n = 0; n < N; ++n) {
-        const double shape = dispersion[n] >= 1.0 ? dispersion[n] : dispersion[n] + 1.0;
-        gd[(size_t)n] = shape - 1.0 / 3.0;
-        gc[(size_t)n] = 1.0 / std::sqrt(9.0 * gd[(size_t)n]);
-    }
-}
-
 }  // namespace
 
 extern "C" int salnmf_nb_refit_exposures(int device, const double* counts, int64_t n_samples, int n_features, const double* signatures, int n_signatures,
@@ -95,9 +84,7 @@ extern "C" int salnmf_draw_nb_counts(int device, const double* exposures, int64_
     CK(check_model_draw(exposures, N, K, signatures, V, B));
     CK(nb_check_dispersion(dispersion, N));
     for (int64_t n = 0; n < N; ++n) {
-        double mean = 0.0;
-        for (int v = 0; v < V; ++v)
-            for (int k = 0; k < K; ++k) mean += exposures[(size_t)n * K + k] * signatures[(size_t)k * V + v];
+        const double mean = nb_model_row_sum(exposures + (size_t)n * K, signatures, K, V);
         if (!(mean <= NB_MAX_MEAN)) return fail("the model's row sums must not exceed 2^24: row %lld sums to %g", (long long)n, mean);
     }
     std::vector<double> gd, gc;

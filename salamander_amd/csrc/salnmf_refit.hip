@@ -205,60 +205,25 @@ extern "C" int salnmf_goodness_of_fit(int device, const double* counts, int64_t 
 // 18) and the profile likelihood with its intervals (salnmf_profile.h, section 19) do alike.  All four entry points run
 // pair_observed; the first two go on with their draws (presence_enqueue, pair_draw_solve) and presence_finish, the power
 // analysis putting its launches on the same stream in between; the last two wait (profile_observed), list their problems on
-// the host, run one profile_kernel launch and scatter its trials.
+// the host, run one profile_kernel launch and scatter its trials.  The shared part is salnmf_refit_drivers.h's pair run, which
+// salnmf_nb_presence.hip instantiates with the negative-binomial model; here it runs with the Poisson one.
 
 namespace {
 
-// The arguments of a pair call.  The first group is every call's; the second the presence test's (null and 0 in a profile call).
-struct PairIO {
-    int device;
-    const double* counts;
-    int64_t N;
-    int V;
-    const double* signatures;
-    int K;
-    const int* test;
-    int S;
-    const uint8_t* candidates;
-    int min_iterations, max_iterations, conv_test_freq;
-    double tol;
-    uint8_t* tested;
-    double *exposures, *errors;  // the alternative fit: (N, K) and (N)
-    double* timings;
-
-    int B;
-    uint64_t seed;
-    int64_t chunk_bytes;
-    double* statistic;
-    int* n_exceed;
-    double *null_mean, *null_exposures, *null_errors;
-    int *n_iterations, *converged;
-    double* null_statistics;
-    int* null_n_iterations;
-    double* draws;
+// The Poisson model of the pair run (salnmf_refit_drivers.h): no inputs of its own, presence_kernel, and the conditional model
+// draw of salnmf_presence.h from the device-resident null fits (a row's trial count is read off the clipped counts)
+struct PoissonPresence {
+    int own_checks() const { return 0; }
+    bool inputs(DevBufs&, PresenceArgs&) const { return true; }
+    int launch(const PresenceArgs& a, int cus, hipStream_t stream) const { return launch_presence(a, cus, stream); }
+    int after_observed(const PairIO&, PairRunOf<PresenceArgs>&) const { return 0; }
+    void draw(PairRunOf<PresenceArgs>& r, uint64_t seed, int first, int count) const {
+        presence_launch_draw(r.dH0, r.dW, r.dX, r.dpn, r.dps, r.dXb, (int64_t)r.NP, r.a.V, r.a.K, seed, SALNMF_EPSILON, first, count, r.d->stream);
+    }
+    int before_wait(DevBufs&) const { return 0; }
 };
 
-// What a call keeps between its launches and its results: the pair list, the observed fits of every pair on the host (stat =
-// f0 - f1, f = (f1, f0), H1), the device buffers later launches read again and the host ends of the asynchronous copies (which
-// live until d's destructor has waited for the stream: d is the last member, and exists once the validation has passed and a
-// pair is tested).
-struct PairRun {
-    RefitInputs in;
-    std::vector<int> pair_n, pair_s;
-    std::vector<size_t> slot;  // pair j is entry slot[j] of the (N, S) results
-    std::vector<double> h_stat, h_f, h_H1;
-    std::vector<double> h_H0, h_mean, h_stat_b, h_draws;  // the presence test's
-    std::vector<int> h_nit, h_conv, h_exceed, h_nit_b;
-    Spans sp;  // presence: draw, solve, reduce; planting, alternative draw, solve, reduce.  profile: the observed launch, the profile launch
-    size_t NP = 0;
-    int64_t chunk_rows = 0;  // rows [pairs][V] of the chunk buffer that chunk_bytes allows
-    int n_chunks = 0;
-    double *dW = nullptr, *dX = nullptr, *dH0 = nullptr, *dstat_b = nullptr, *dXb = nullptr;
-    int *dpn = nullptr, *dps = nullptr;
-    uint32_t* dcand = nullptr;
-    PresenceArgs a{};  // the observed launch's
-    std::unique_ptr<DevBufs> d;
-
+struct PairRun : PairRunOf<PresenceArgs> {
     int launch_profile_kernel(const PairIO& io, ProfileArgs pa) {
         pa.X = dX, pa.W = dW, pa.cand = dcand, pa.next_tile = a.next_tile;
         pa.V = io.V, pa.K = io.K, pa.min_it = io.min_iterations, pa.max_it = io.max_iterations, pa.freq = io.conv_test_freq, pa.tol = io.tol;
@@ -272,221 +237,12 @@ struct PairRun {
     }
 };
 
-int presence_check_test(const int* test, int S, int K) {
-    if (S < 1 || S > REFIT_KMAX) return fail("n_test must be in [1, %d], got %d", REFIT_KMAX, S);
-    for (int j = 0; j < S; ++j) {
-        if (test[j] < 0 || test[j] >= K) return fail("tested signature %d is not in [0, %d)", test[j], K);
-        for (int i = 0; i < j; ++i)
-            if (test[i] == test[j]) return fail("signature %d is tested twice", test[j]);
-    }
-    return 0;
-}
-
-// The tested pairs, sample after sample: s is a candidate and not the only one.  Pair j is entry slot[j] of the (N, S) results.
-void presence_list_pairs(const RefitInputs& in, int64_t N, int K, const int* test, int S, bool with_candidates, uint8_t* tested, std::vector<int>& pair_n,
-                         std::vector<int>& pair_s, std::vector<size_t>& slot) {
-    const int words = ((K + 15) / 16 + 1) / 2;
-    for (int64_t n = 0; n < N; ++n) {
-        int size = K;
-        if (with_candidates) {
-            size = 0;
-            for (int w = 0; w < words; ++w) size += __builtin_popcount(in.cand[(size_t)n * words + w]);
-        }
-        for (int j = 0; j < S; ++j) {
-            const int s = test[j];
-            const bool member = !with_candidates || ((in.cand[(size_t)n * words + (s >> 5)] >> (s & 31)) & 1u);
-            tested[(size_t)n * S + j] = member && size > 1;
-            if (member && size > 1) pair_n.push_back((int)n), pair_s.push_back(s), slot.push_back((size_t)n * S + j);
-        }
-    }
-}
-
-// What follows a call's own null checks: the rest of the validation (integer counts only where draws will be made of them), the
-// pair list, the untested entries of the alternative fit, and -- with a tested pair -- the uploads and the observed launch under
-// span `span`: the alternative solve on C, then the null solve (which is the frozen solve at 0.0), and the copies of stat, f and
-// H1 back.  Nothing is waited for; h0 (r.dH0, [pairs][K]) stays on the device.
-int pair_observed(const PairIO& io, bool integer_counts, int span, PairRun& r) {
-    const int64_t N = io.N;
-    const int V = io.V, K = io.K, S = io.S;
-    if (io.conv_test_freq >= 1 && io.max_iterations >= 0 && io.max_iterations % io.conv_test_freq != 0)
-        return fail("max_iterations must be a multiple of conv_test_freq, got %d and %d", io.max_iterations, io.conv_test_freq);
-    CK(presence_check_test(io.test, S, K));
-    RefitInputs& in = r.in;
-    CK(refit_prepare(io.device, io.counts, N, V, io.signatures, K, 0, 0, nullptr, io.min_iterations, io.max_iterations, io.conv_test_freq, io.tol, true,
-                     in, AssignSets{io.candidates, nullptr, 0}));
-    if (integer_counts) CK(refit_check_counts(io.counts, N, V, in.icounts));  // row totals below 2^32 too (the values themselves are not used)
-    presence_list_pairs(in, N, K, io.test, S, io.candidates != nullptr, io.tested, r.pair_n, r.pair_s, r.slot);
-    const size_t NP = r.NP = r.pair_n.size();
-    if (NP > 0x7fffffff) return fail("%zu tested pairs: at most 2^31 - 1", NP);
-    const double nan = std::nan("");
-    std::fill(io.exposures, io.exposures + (size_t)N * K, nan);
-    std::fill(io.errors, io.errors + N, nan);
-    if (NP == 0) return 0;
-
-    const size_t PK = NP * K;
-    r.h_stat.resize(NP), r.h_f.resize(2 * NP), r.h_H1.resize(PK);
-    r.d.reset(new DevBufs);
-    DevBufs& d = *r.d;
-    CK(d.own_stream());
-    r.dW = upload(d, io.signatures, (size_t)K * V);
-    r.dX = upload(d, in.x);
-    r.dpn = upload(d, r.pair_n);
-    r.dps = upload(d, r.pair_s);
-    r.dcand = io.candidates ? upload(d, in.cand) : nullptr;
-    double* dstat = d.get<double>(NP);
-    double* df = d.get<double>(2 * NP);
-    int* dnit = d.get<int>(2 * NP);
-    int* dconv = d.get<int>(2 * NP);
-    double* dH1 = d.get<double>(PK);
-    r.dH0 = d.get<double>(PK);
-    unsigned* dnext = d.get<unsigned>(1);
-    if (!r.dW || !r.dX || !r.dpn || !r.dps || !dstat || !df || !dnit || !dconv || !dH1 || !r.dH0 || !dnext || (io.candidates && !r.dcand))
-        return fail("hipMalloc or upload failed (%zu pairs x %d, %d signatures)", NP, V, K);
-    r.sp.start(d, io.timings != nullptr);
-    r.a = PresenceArgs{r.dX, r.dW, r.dpn, r.dps, r.dcand, dstat, dnit, df, dconv, dH1, r.dH0, dnext, (int64_t)NP, (int64_t)NP, V, K, 1,
-                       io.min_iterations, io.max_iterations, io.conv_test_freq, io.tol};
-    CK(r.sp.timed(span, [&] { return launch_presence(r.a, in.cus, d.stream); }));
-    CK(download(d, r.h_stat, dstat));
-    CK(download(d, r.h_f, df));
-    CK(download(d, r.h_H1, dH1));
-    return 0;
-}
-
-// (after the stream has been waited for) a sample's alternative fit is that of its first tested pair: every tested pair of a
-// sample solves the same problem on C and holds the same bits
-void pair_scatter_alternative(const PairIO& io, const PairRun& r) {
-    const int K = io.K;
-    for (size_t j = 0; j < r.NP; ++j)
-        if (j == 0 || r.pair_n[j - 1] != r.pair_n[j]) {
-            const size_t n = (size_t)r.pair_n[j];
-            std::copy(r.h_H1.begin() + j * K, r.h_H1.begin() + (j + 1) * K, io.exposures + n * K);
-            io.errors[n] = r.h_f[2 * j];
-        }
-}
-
-// Draw rows first .. of `rows` into the chunk buffer (draw(first, count) launches the draw of `count` rows [pairs][V] into
-// r.dXb), `chunk` at a time, and solve them as the observed launch solved the counts: a draw's problems keep their statistic
-// (stat [rows][pairs]) and iteration counts (nit [rows][pairs][2]) only.  host_copy, if not null, gets the drawn rows.
-template <typename Draw>
-int pair_draw_solve(PairRun& r, int64_t rows, int64_t chunk, Draw&& draw, double* stat, int* nit, double* host_copy, int span_draw, int span_solve,
-                    int* n_chunks) {
-    DevBufs& d = *r.d;
-    const size_t NP = r.NP, PV = NP * r.a.V;
-    for (int64_t first = 0; first < rows; first += chunk, ++*n_chunks) {
-        const int64_t count = std::min(chunk, rows - first);
-        CK(r.sp.timed(span_draw, [&]() -> int {
-            draw(first, count);
-            HIPCK(hipGetLastError());
-            return 0;
-        }));
-        if (host_copy) CK(download(d, host_copy + (size_t)first * PV, r.dXb, (size_t)count * PV));
-        PresenceArgs c = r.a;
-        c.X = r.dXb;
-        c.by_sample = 0;
-        c.P = count * (int64_t)NP;
-        c.stat = stat + (size_t)first * NP;
-        c.nit = nit + 2 * (size_t)first * NP;
-        c.f = nullptr, c.conv = nullptr, c.H1 = nullptr, c.H0 = nullptr;
-        CK(r.sp.timed(span_solve, [&] { return launch_presence(c, r.in.cus, d.stream); }));
-    }
-    return 0;
-}
-
-// Validation, the pair list, the untested entries of the results, and -- with a tested pair -- everything the presence test puts
-// on the stream: pair_observed, the null chunks, the reduction and the downloads.  Nothing is waited for.  The null statistics
-// (r.dstat_b, [B][pairs]) stay on the device; the chunk buffer r.dXb holds min(max(B, other_rows), r.chunk_rows) rows, so that a
-// caller with other_rows draws of its own can reuse it.
-int presence_enqueue(const PairIO& io, int64_t other_rows, PairRun& r) {
-    const int64_t N = io.N;
-    const int V = io.V, K = io.K, S = io.S, B = io.B;
-    if (!io.counts || !io.signatures || !io.test || !io.tested || !io.statistic || !io.n_exceed || !io.null_mean || !io.exposures || !io.errors ||
-        !io.null_exposures || !io.null_errors || !io.n_iterations || !io.converged || !io.null_statistics || !io.null_n_iterations)
-        return fail("null argument");
-    CK(check_n_draws(B));
-    CK(pair_observed(io, true, 1, r));
-    const size_t NS = (size_t)N * S, NP = r.NP;
-    const double nan = std::nan("");
-    std::fill(io.statistic, io.statistic + NS, nan);
-    std::fill(io.null_mean, io.null_mean + NS, nan);
-    std::fill(io.null_errors, io.null_errors + NS, nan);
-    std::fill(io.n_exceed, io.n_exceed + NS, 0);
-    std::fill(io.null_exposures, io.null_exposures + NS * K, nan);
-    std::fill(io.n_iterations, io.n_iterations + 2 * NS, 0);
-    std::fill(io.converged, io.converged + 2 * NS, 0);
-    std::fill(io.null_statistics, io.null_statistics + (size_t)B * NS, nan);
-    std::fill(io.null_n_iterations, io.null_n_iterations + 2 * (size_t)B * NS, 0);
-    if (io.draws) std::fill(io.draws, io.draws + (size_t)B * NS * V, 0.0);
-    if (io.timings) io.timings[0] = io.timings[1] = io.timings[2] = io.timings[3] = 0.0;
-    if (NP == 0) return 0;
-
-    // draws per chunk: the [chunk][pairs][V] buffer stays within chunk_bytes (at least one draw)
-    const size_t PV = NP * V, PK = NP * K, PB = NP * B;
-    r.chunk_rows = chunk_rows(io.chunk_bytes, sizeof(double) * PV, INT64_MAX);
-    const int64_t buffer_rows = std::min<int64_t>(std::max<int64_t>(B, other_rows), r.chunk_rows);
-    r.h_H0.resize(PK), r.h_mean.resize(NP), r.h_stat_b.resize(PB), r.h_draws.resize(io.draws ? PB * V : 0);
-    r.h_nit.resize(2 * NP), r.h_conv.resize(2 * NP), r.h_exceed.resize(NP), r.h_nit_b.resize(2 * PB);
-    DevBufs& d = *r.d;
-    r.dXb = d.get<double>((size_t)buffer_rows * PV);
-    r.dstat_b = d.get<double>(PB);
-    int* dnit_b = d.get<int>(2 * PB);
-    int* dexceed = d.get<int>(NP);
-    double* dmean = d.get<double>(NP);
-    if (!r.dXb || !r.dstat_b || !dnit_b || !dexceed || !dmean) return fail("hipMalloc failed (%d draws of %zu pairs x %d, %d signatures)", B, NP, V, K);
-    // from the device-resident exposures of the observed null fits; a row's trial count is read off the clipped counts
-    CK(pair_draw_solve(r, B, std::min<int64_t>(B, r.chunk_rows), [&](int64_t first, int64_t count) {
-        presence_launch_draw(r.dH0, r.dW, r.dX, r.dpn, r.dps, r.dXb, (int64_t)NP, V, K, io.seed, SALNMF_EPSILON, (int)first, (int)count, d.stream);
-    }, r.dstat_b, dnit_b, io.draws ? r.h_draws.data() : nullptr, 0, 1, &r.n_chunks));
-    // gof_reduce_kernel over the pairs: n_exceed counts t_b >= t (false for a NaN on either side), null_mean sums from 0.0 in ascending b
-    const GofReduceArgs red{r.a.stat, r.dstat_b, dexceed, dmean, (int64_t)NP, B};
-    CK(r.sp.timed(2, [&]() -> int {
-        gof_launch_reduce(red, d.stream);
-        HIPCK(hipGetLastError());
-        return 0;
-    }));
-    CK(download(d, r.h_nit, r.a.nit));
-    CK(download(d, r.h_conv, r.a.conv));
-    CK(download(d, r.h_H0, r.dH0));
-    CK(download(d, r.h_exceed, dexceed));
-    CK(download(d, r.h_mean, dmean));
-    CK(download(d, r.h_stat_b, r.dstat_b));
-    CK(download(d, r.h_nit_b, dnit_b));
-    return 0;
-}
-
-// Waits for the stream, then the compact pair list back into the (N, S) results and the first four timings.
-int presence_finish(const PairIO& io, PairRun& r) {
-    const int V = io.V, K = io.K, B = io.B;
-    const size_t NP = r.NP, NS = (size_t)io.N * io.S;
-    HIPCK(hipStreamSynchronize(r.d->stream));
-    pair_scatter_alternative(io, r);
-    for (size_t j = 0; j < NP; ++j) {
-        const size_t o = r.slot[j];
-        io.statistic[o] = r.h_stat[j];
-        io.n_exceed[o] = r.h_exceed[j];
-        io.null_mean[o] = r.h_mean[j];
-        io.null_errors[o] = r.h_f[2 * j + 1];
-        std::copy(r.h_H0.begin() + j * K, r.h_H0.begin() + (j + 1) * K, io.null_exposures + o * K);
-        for (int i = 0; i < 2; ++i) io.n_iterations[2 * o + i] = r.h_nit[2 * j + i], io.converged[2 * o + i] = r.h_conv[2 * j + i];
-        for (size_t b = 0; b < (size_t)B; ++b) {
-            io.null_statistics[b * NS + o] = r.h_stat_b[b * NP + j];
-            for (int i = 0; i < 2; ++i) io.null_n_iterations[2 * (b * NS + o) + i] = r.h_nit_b[2 * (b * NP + j) + i];
-            if (io.draws)  // plain counts: the clipped zeros restored to 0
-                for (int v = 0; v < V; ++v) {
-                    const double c = r.h_draws[(b * NP + j) * V + v];
-                    io.draws[(b * NS + o) * V + v] = c < 1.0 ? 0.0 : c;
-                }
-        }
-    }
-    CK(r.sp.totals(3, io.timings));
-    if (io.timings) io.timings[3] = (double)r.n_chunks;
-    return 0;
-}
-
 // The profile calls' start: pair_observed (the counts need not be integers: nothing is drawn), waited for, and the alternative
 // fit scattered.
 int profile_observed(const PairIO& io, PairRun& r) {
     if (!io.counts || !io.signatures || !io.test || !io.tested || !io.exposures || !io.errors) return fail("null argument");
-    CK(pair_observed(io, false, 0, r));
+    PoissonPresence m;
+    CK(pair_observed(io, false, 0, r, m));
     if (io.timings) io.timings[0] = io.timings[1] = io.timings[2] = 0.0;
     if (r.NP == 0) return 0;
     HIPCK(hipStreamSynchronize(r.d->stream));
@@ -505,8 +261,9 @@ extern "C" int salnmf_signature_presence(int device, const double* counts, int64
     const PairIO io{device, counts, n_samples, n_features, signatures, n_signatures, test, n_test, candidates, min_iterations, max_iterations,
                     conv_test_freq, tol, tested, exposures, errors, timings, n_draws, seed, chunk_bytes, statistic, n_exceed, null_mean, null_exposures,
                     null_errors, n_iterations, converged, null_statistics, null_n_iterations, draws};
+    PoissonPresence m;
     PairRun r;
-    CK(presence_enqueue(io, 0, r));
+    CK(presence_enqueue(io, 0, r, m));
     if (r.NP == 0) return 0;
     return presence_finish(io, r);
 }
@@ -536,8 +293,9 @@ extern "C" int salnmf_signature_power(int device, const double* counts, int64_t 
                     null_errors, n_iterations, converged, null_statistics, null_n_iterations, draws};
     std::vector<double> h_Hp, h_stat_a, h_mean_a, h_draws_a;  // (before r: they outlive the copies into them, which r.d waits for)
     std::vector<int> h_nit_a, h_exceed_a, h_ndet;
+    PoissonPresence m;
     PairRun r;
-    CK(presence_enqueue(io, R, r));
+    CK(presence_enqueue(io, R, r, m));
     const int64_t N = n_samples;
     const int V = n_features, K = n_signatures, S = n_test;
     const size_t NS = (size_t)N * S, NP = r.NP;
@@ -572,7 +330,7 @@ extern "C" int salnmf_signature_power(int device, const double* counts, int64_t 
     }));
     // rows per chunk: the presence test's buffer and rule
     int n_chunks = 0;
-    CK(pair_draw_solve(r, R, std::min<int64_t>(R, r.chunk_rows), [&](int64_t first, int64_t count) {
+    CK(pair_draw_solve(r, m, R, std::min<int64_t>(R, r.chunk_rows), [&](int64_t first, int64_t count) {
         power_launch_draw(dHp, r.dW, r.dX, r.dpn, r.dps, r.dXb, (int64_t)NP, V, K, seed, SALNMF_EPSILON, A, first, count, d.stream);
     }, dstat_a, dnit_a, alt_draws ? h_draws_a.data() : nullptr, 4, 5, &n_chunks));
     CK(r.sp.timed(6, [&]() -> int {

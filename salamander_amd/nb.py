@@ -13,19 +13,22 @@ device (``csrc/salnmf_nbdraw.h``), :func:`nb_goodness_of_f
 dispersion estimate: a p-value for ``lr_statistic`` and an interval for the estimate.  :func:`nb_assign_signatures` is
 :func:`assign_signatures <salamander_amd.assign.assign_signatures>` under the negative-binomial model (``csrc/salnmf_nb_assign.h``,
 DESIGN.md section 25): which signatures are active in each sample, with candidate sets, required signatures and the re-addition
-pass.  There is no CPU fallback.
+pass.  :func:`nb_signature_presence_test` is
+:func:`signature_presence_test <salamander_amd.presence.signature_presence_test>` under that model (``csrc/salnmf_nb_presence.h``,
+DESIGN.md section 26): is signature s present in this sample, when the counts are overdispersed?  There is no CPU fallback.
 """
 
 from __future__ import annotations
 
 import time
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, fields
 
 import numpy as np
 
 from . import _lib
 from .assign import AssignResult, assign_signatures, call_assign, check_sets, check_threshold
 from .gof import GofResult, call_gof, check_integer_counts, check_model, check_n_draws, draw_model_counts
+from .presence import PresenceResult, call_presence, check_presence_arguments
 from .refit import RefitResult, call_refit, check_arguments, quantile_indices, refit_exposures
 from .resample import check_seed
 
@@ -340,6 +343,47 @@ def nb_goodness_of_fit(counts, signatures, dispersion, n_draws: int = 200, seed:
                               count_failed=True)
     _failed_rows(failed, "nb_goodness_of_fit")
     return NBGofResult(**fields, dispersion=alpha, log_likelihood=-fields["reconstruction_errors"] + nb_constant(X, alpha))
+
+
+@dataclass
+class NBPresenceResult(PresenceResult):
+    """:class:`PresenceResult <salamander_amd.presence.PresenceResult>` of the negative-binomial model: ``reconstruction_errors``,
+    ``null_errors`` and the statistics are negative-binomial divergences and their differences, plus the dispersions used and the
+    log-likelihoods of the two fits."""
+
+    dispersion: np.ndarray | None = None  # (N,)
+    log_likelihood: np.ndarray | None = None  # (N,): the alternative's, -reconstruction_errors + nb_constant(counts, dispersion)
+    null_log_likelihood: np.ndarray | None = None  # (N, S): -null_errors + nb_constant(counts, dispersion)
+
+
+def nb_signature_presence_test(counts, signatures, dispersion, test, n_draws: int = 200, seed: int = 0, candidates=None, keep_draws: bool = False,
+                               min_iterations: int = 500, max_iterations: int = 10000, conv_test_freq: int = 10, tol: float = 1e-7,
+                               chunk_bytes: int | None = None, device: int = 0) -> NBPresenceResult:
+    """The bootstrap likelihood-ratio test of every signature in ``test`` in every row of ``counts (N, V)`` against the fixed
+    ``signatures (K, V)`` under the negative-binomial model with ``dispersion`` (a scalar or one value per sample, in (0, 1e6]).
+
+    :func:`signature_presence_test <salamander_amd.presence.signature_presence_test>` with the step and the divergence of
+    :func:`nb_refit_exposures` and the draw of :func:`draw_nb_counts`.  With C the sample's candidate set and s = ``test[j]``: the
+    alternative is ``nb_assign_signatures(x, signatures, dispersion, candidates=C, required=C, ...)`` and the null the same call on
+    C without s, bit for bit; ``statistic[n, j] = f0 - f1`` is a difference of two negative-binomial divergences at one dispersion,
+    a log-likelihood difference.  Null draw b is a gamma-Poisson draw from the fit without s with the sample's dispersion and goes
+    through the same two solves.  Unlike the Poisson test the null vectors are **not conditional on the sample's total**: the
+    negative-binomial refit leaves the scale free, and null totals vary as in :func:`nb_goodness_of_fit`.  On overdispersed counts
+    the Poisson test's null is too tight and it rejects too often; this one's null carries the variance ``p + p**2 / dispersion``.
+    Untested pairs, ``p_value``, ``max_iterations`` and ``chunk_bytes`` as in the Poisson test.  The counts are non-negative
+    integers; a null fit whose mean total exceeds 2**24 is a ``RuntimeError`` from the library; everything else out of range is a
+    ``ValueError`` before the device is touched."""
+    t_start = time.perf_counter()
+    X, W, T, C, B, seed, min_it, max_it, freq, tol, chunk = check_presence_arguments(counts, signatures, test, n_draws, seed, candidates, min_iterations,
+                                                                                     max_iterations, conv_test_freq, tol, chunk_bytes)
+    alpha = check_dispersion(dispersion, X.shape[0])
+    out, ms, failed = call_presence("salnmf_nb_signature_presence", (alpha,), X, W, T, C, B, seed, min_it, max_it, freq, tol, chunk, keep_draws, device,
+                                    count_failed=True)
+    _failed_rows(failed, "nb_signature_presence_test")
+    res = out.result(T, C, ms, time.perf_counter() - t_start)
+    const = nb_constant(X, alpha)
+    return NBPresenceResult(**{f.name: getattr(res, f.name) for f in fields(res)}, dispersion=alpha, log_likelihood=-res.reconstruction_errors + const,
+                            null_log_likelihood=-res.null_errors + const[:, None])
 
 
 def _cohort_profiles(cohorts, S, g, poisson: bool, it, device):

@@ -101,6 +101,24 @@ class PresenceOutputs:
                               draws=self.drawn, timings=timings)
 
 
+def call_presence(symbol, model_args, X, W, T, C, B, seed, min_it, max_it, freq, tol, chunk, keep_draws, device, count_failed=False):
+    """One ``salnmf_*signature_presence`` call on checked arguments: the outputs' allocation and the call of ``symbol`` with
+    ``model_args`` (the model's own arrays) after K and, with ``count_failed``, a trailing output for the rows no draw could be
+    made for.  Returns ``(the PresenceOutputs, the four timings, that count)``."""
+    (N, V), K, S = X.shape, W.shape[0], int(T.size)
+    lib = _lib.load_with_device()
+    out = PresenceOutputs(N, V, K, S, B, keep_draws)
+    Cb = None if C is None else C.astype(np.uint8)
+    failed = np.zeros(1, dtype=np.int32)
+    ms = (c_double * 4)()
+    p = _lib.pointer
+    _lib.check(getattr(lib, symbol)(
+        int(device), p(X), N, V, p(W), K, *(p(m) for m in model_args), p(T), S, p(Cb), B, seed, min_it, max_it, freq, tol, chunk, *out.pointers(),
+        ctypes.cast(ms, _lib._D), *([p(failed)] if count_failed else []),
+    ))
+    return out, ms, int(failed[0])
+
+
 def signature_presence_test(counts, signatures, test, n_draws: int = 200, seed: int = 0, candidates=None, min_iterations: int = 500,
                             max_iterations: int = 10000, conv_test_freq: int = 10, tol: float = 1e-7, chunk_bytes: int | None = None,
                             keep_draws: bool = False, device: int = 0) -> PresenceResult:
@@ -120,13 +138,5 @@ def signature_presence_test(counts, signatures, test, n_draws: int = 200, seed: 
     t_start = time.perf_counter()
     X, W, T, C, B, seed, min_it, max_it, freq, tol, chunk = check_presence_arguments(counts, signatures, test, n_draws, seed, candidates, min_iterations,
                                                                                      max_iterations, conv_test_freq, tol, chunk_bytes)
-    (N, V), K, S = X.shape, W.shape[0], int(T.size)
-    lib = _lib.load_with_device()
-    out = PresenceOutputs(N, V, K, S, B, keep_draws)
-    Cb = None if C is None else C.astype(np.uint8)
-    ms = (c_double * 4)()
-    p = _lib.pointer
-    _lib.check(lib.salnmf_signature_presence(
-        int(device), p(X), N, V, p(W), K, p(T), S, p(Cb), B, seed, min_it, max_it, freq, tol, chunk, *out.pointers(), ctypes.cast(ms, _lib._D),
-    ))
+    out, ms, _ = call_presence("salnmf_signature_presence", (), X, W, T, C, B, seed, min_it, max_it, freq, tol, chunk, keep_draws, device)
     return out.result(T, C, ms, time.perf_counter() - t_start)
